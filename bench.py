@@ -1,7 +1,12 @@
 #!/usr/bin/env python3
 """bench.py -- factorize throughput of the MI355X hot path (BASELINE.json metric).
 
-  python bench.py --gpus N --steps K --warmup W [--config C3|C2|C4]
+  python bench.py --gpus N --steps K --warmup W [--config C3|C2|C4] [--dump-outputs DIR] [--full]
+
+A plain run sets up, warms up, times the K steps and prints the result line, nothing else.  --full adds the secondary
+measurements: the batched legs (`batched`, `batched_other_sizes`, each verified against the CPU oracle) and the CPU
+baseline (`cpu_baseline`).  --dump-outputs DIR writes what the last timed step computed (the factors and statistics a
+caller of factorize receives; C5: the last solution and the per-modification results) as DIR/<name>.npy in float64.
 
 A "step" is one factorize (singletons -> setup_bump -> pivot loop -> build/read-out -> statistics tail, all on
 the device) of one synthetic LP basis per GPU, with B already resident in HBM when the clock starts.  The
@@ -40,12 +45,37 @@ def parse_args(argv=None):
     ap.add_argument("--config", default="C3", choices=["C2", "C3", "C4", "C5"])
     ap.add_argument("--mods", type=int, default=1000, help="C5: column modifications per step")
     ap.add_argument("--block", type=int, default=0, help="workgroup size of the pivot kernel (debug)")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-batch-sizes", action="store_true", help="skip the batched measurement on C4- and C2-size bases")
-    ap.add_argument("--batch", type=int, default=1536, help="bases in flight for the secondary throughput measurement (0 = skip)")
-    ap.add_argument("--no-verify", action="store_true", help="skip the untimed oracle check of the batched legs")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the last timed step computed as DIR/<name>.npy (float64, at most 64 MB in all)")
+    ap.add_argument("--full", action="store_true",
+                    help="also run the secondary measurements: batched legs (with their oracle check) and the CPU baseline")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="--full: skip the CPU baseline")
+    ap.add_argument("--no-batch-sizes", action="store_true", help="--full: skip the batched measurement on C4- and C2-size bases")
+    ap.add_argument("--batch", type=int, default=1536, help="--full: bases in flight for the secondary throughput measurement (0 = skip)")
+    ap.add_argument("--no-verify", action="store_true", help="--full: skip the untimed oracle check of the batched legs")
     ap.add_argument("--batch-block", type=int, default=256, help="workgroup size of the multi-wave pivot kernel in batch mode (BLU_PIVOT_KERNEL=2 only)")
     return ap.parse_args(argv)
+
+
+DUMP_BUDGET_BYTES = 64 << 20
+
+
+def dump_outputs(outdir, arrays, budget=DUMP_BUDGET_BYTES):
+    """Write `arrays` (name -> 1-d array) as outdir/<name>.npy in float64 (integer arrays are exact there: every index is
+    far below 2**53).  If they do not fit into `budget` bytes together, every array is cut to a fixed seeded sample of
+    its positions (the same positions in every run of the same length), written beside it as <name>_sample_idx.npy."""
+    import numpy as np
+    os.makedirs(outdir, exist_ok=True)
+    arrays = {k: np.ascontiguousarray(a, dtype=np.float64).ravel() for k, a in arrays.items()}
+    total = sum(a.nbytes for a in arrays.values())
+    frac = 1.0 if total <= budget else budget / (2.0 * total)  # (sample and positions both count)
+    for name, a in sorted(arrays.items()):
+        if frac < 1.0 and len(a) > 1:
+            rng = np.random.default_rng(len(a))
+            idx = np.sort(rng.choice(len(a), max(1, int(len(a) * frac)), replace=False))
+            np.save(os.path.join(outdir, name + "_sample_idx.npy"), idx.astype(np.float64))
+            a = a[idx]
+        np.save(os.path.join(outdir, name + ".npy"), a)
 
 
 def kernel_source_sha16():
@@ -255,16 +285,20 @@ def bench_c5(args):
         f0 = sum(h.stat(k) for k in (K.STAT_L_FLOPS, K.STAT_U_FLOPS, K.STAT_R_FLOPS))
         t0 = time.perf_counter()
         d = s_ = nz = 0
+        xtbls, statuses = [], []  # per modification: the pivot element and the status of update (1000: not called)
         for j, rows, vals in mods:
             assert h.solve_for_update([j], None, "T") == K.OK
             nz += h.nzlhs
             assert h.solve_for_update(rows, vals, "N") == K.OK
             nz += h.nzlhs
             xtbl = h.lhs[j]
+            xtbls.append(xtbl)
             if abs(xtbl) < 1e-3:  # the replacement would make the basis (nearly) singular: not applied
                 s_ += 1
+                statuses.append(1000)
                 continue
             st = h.update(xtbl)
+            statuses.append(st)
             if st == K.ERROR_SINGULAR_UPDATE:
                 s_ += 1
                 continue
@@ -277,6 +311,13 @@ def bench_c5(args):
             skipped += s_
             nzl += nz
             flops += sum(h.stat(k) for k in (K.STAT_L_FLOPS, K.STAT_U_FLOPS, K.STAT_R_FLOPS)) - f0
+    if args.dump_outputs:
+        # what the caller received in the last step: the last solution (dense and its pattern), every pivot element and
+        # update status, and the update statistics at the end
+        upd = [h.stat(k) for k in (K.STAT_NUPDATE, K.STAT_NFORREST, K.STAT_PIVOT_ERROR, K.STAT_R_NZ, K.STAT_L_NZ, K.STAT_U_NZ,
+                                   K.STAT_MAX_ETA)]
+        dump_outputs(args.dump_outputs, {"lhs": h.lhs, "ilhs": h.ilhs[:h.nzlhs], "xtbl": np.array(xtbls),
+                                         "update_status": np.array(statuses), "update_stats": np.array(upd)})
     nmod = args.steps * len(mods)
     gbs = (16.0 * flops + 16.0 * nzl) / tot_t / 1e9
     out = {"metric": "Forrest-Tomlin update + sparse re-solve: column modifications/s, 100k x 100k basis", "value": nmod / tot_t,
@@ -367,6 +408,18 @@ def rank_main(args, backend=None, device=None):
     fence()
     elapsed = shard.max_over_ranks(time.perf_counter() - t0, dev)
     total_nnz = shard.sum_over_ranks(nnz, dev)
+    if args.dump_outputs:
+        # what a caller of the timed path receives from the last step: the factors of get_factors and the statistics
+        # that are results rather than timings (the ones the batched legs compare with the oracle)
+        outs = h.get_factors()
+        stat_keys = [K.STAT_RANK, K.STAT_MATRIX_NZ, K.STAT_BUMP_SIZE, K.STAT_BUMP_NZ, K.STAT_L_NZ, K.STAT_U_NZ, K.STAT_NSEARCH_PIVOT,
+                     K.STAT_FACTOR_FLOPS, K.STAT_RANKDEF, 50, 51, 52, 53, 54, 55, 56, K.STAT_MIN_PIVOT, K.STAT_MAX_PIVOT,
+                     K.STAT_CONDEST_L, K.STAT_CONDEST_U, K.STAT_NORM_L, K.STAT_NORM_U, K.STAT_NORMEST_L_INV,
+                     K.STAT_NORMEST_U_INV, K.STAT_ONENORM, K.STAT_INFNORM, K.STAT_RESIDUAL_TEST]
+        outs["stats"] = np.array([h.stat(k) for k in stat_keys])
+        if world > 1:
+            outs = {"rank%d_%s" % (rank, k): a for k, a in outs.items()}
+        dump_outputs(args.dump_outputs, outs, DUMP_BUDGET_BYTES // world)
 
     F = h.stat(K.STAT_FACTOR_FLOPS)
     l_nz, u_nz = h.stat(K.STAT_L_NZ), h.stat(K.STAT_U_NZ)
@@ -433,7 +486,7 @@ def rank_main(args, backend=None, device=None):
         "phases_last_step": phases,
         "roofline_onnz_kernels": o_rows,
     }
-    if args.batch > 0 and not stub:
+    if args.full and args.batch > 0 and not stub:
         out["batched"] = batched_throughput(args, c, dev, local_rank, world, backend)
         if args.config == "C3" and not args.no_batch_sizes:
             # the same measurement on smaller bases, of which more fit into HBM (the batch kernel is limited by the number
@@ -441,7 +494,7 @@ def rank_main(args, backend=None, device=None):
             out["batched_other_sizes"] = [
                 batched_throughput(args, dict(CONFIGS["C4"]), dev, local_rank, world, backend, B=3072, cfg_name="C4"),
                 batched_throughput(args, dict(CONFIGS["C2"]), dev, local_rank, world, backend, B=4096, cfg_name="C2")]
-    if rank == 0 and not args.no_cpu_baseline:
+    if args.full and rank == 0 and not args.no_cpu_baseline:
         c0 = CONFIGS[args.config]
         cp0, ri0, v0 = (cp, ri, v) if c["seed"] == c0["seed"] else backend.gen_lp_basis(c0["m"], c0["k"], c0["bw"], c0["tri_frac"], c0["seed"], c0["offscale"])
         out["cpu_baseline"] = cpu_baseline(cp0, ri0, v0, args.config)

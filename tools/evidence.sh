@@ -13,10 +13,10 @@ E=$R/gpurun_out/ev
 mkdir -p $E
 cd $R
 if [ "${1:-1}" = "1" ]; then
-timeout -k 10 600 python bench.py > $E/bench_c3.json 2> $E/bench_c3.err || { echo "bench C3 failed"; tail -5 $E/bench_c3.err; exit 1; }
+timeout -k 10 600 python bench.py --full > $E/bench_c3.json 2> $E/bench_c3.err || { echo "bench C3 failed"; tail -5 $E/bench_c3.err; exit 1; }
 echo "bench C3 done"
-timeout -k 10 300 python bench.py --config C2 --steps 5 --batch 4096 --no-batch-sizes > $E/bench_c2.json 2> $E/bench_c2.err || echo "bench C2 failed"
-timeout -k 10 300 python bench.py --config C4 --steps 5 --batch 3072 --no-batch-sizes > $E/bench_c4.json 2> $E/bench_c4.err || echo "bench C4 failed"
+timeout -k 10 300 python bench.py --config C2 --steps 5 --full --batch 4096 --no-batch-sizes > $E/bench_c2.json 2> $E/bench_c2.err || echo "bench C2 failed"
+timeout -k 10 300 python bench.py --config C4 --steps 5 --full --batch 3072 --no-batch-sizes > $E/bench_c4.json 2> $E/bench_c4.err || echo "bench C4 failed"
 timeout -k 10 300 python bench.py --config C5 --steps 1 --warmup 0 > $E/bench_c5.json 2> $E/bench_c5.err || echo "bench C5 failed"
 echo "benches done"
 ( cd /tmp && export TMPDIR=/tmp && rocprofv3 --kernel-trace --stats -d $E/prof_c3 -o c3 --output-format csv -- python3 $R/bench.py --steps 5 --warmup 1 --batch 0 --no-cpu-baseline > $E/prof_c3.log 2>&1 )
