@@ -522,6 +522,7 @@ struct GridWs {                        // global scratch of a GridScope (zeroed 
     int part[2][SCOPE_MAX_BLOCKS];
     long long partll[2][SCOPE_MAX_BLOCKS];
     int ctr[8];
+    int nlong; // k_stats_tail_a -> k_stats_tail_b: rows of B of more than 256 entries left to the long-row pass
 };
 struct BlockScope {
     int *sh;        // 40 ints of LDS

@@ -336,7 +336,9 @@ __global__ void __launch_bounds__(CHAIN_THREADS) k_stats_chains(DevLU *Ds, Finis
     if (!ok && threadIdx.x == 0) atomicMax(defect, L->abort ? L->abort : 99);
 }
 
-// The passes over the columns and rows of B, L, U on TAIL_BLOCKS workgroups; per-workgroup maxima to the grid scratch
+// The passes over the columns and rows of B, L, U on TAIL_BLOCKS workgroups; per-workgroup maxima to the grid scratch.
+// Rows of more than 256 entries are only recorded (gw->nlong, zeroed with the grid scratch before k_rows_grid): k_stats_tail_b
+// sums them.
 #define TAIL_BLOCKS 64
 __global__ void __launch_bounds__(1024) k_stats_tail_a(DevLU *Ds, FinishOut *Os, GridWs *gw)
 {
@@ -346,7 +348,8 @@ __global__ void __launch_bounds__(1024) k_stats_tail_a(DevLU *Ds, FinishOut *Os,
     __shared__ double red[4][40];
     if (S->status != ST_DONE || D.skip_stats) return;
     double v[4];
-    stats_tail_loops<false>(D, O, (int)(blockIdx.x * blockDim.x + threadIdx.x), (int)(gridDim.x * blockDim.x), v[0], v[1], v[2], v[3]);
+    stats_tail_loops<false>(D, O, (int)(blockIdx.x * blockDim.x + threadIdx.x), (int)(gridDim.x * blockDim.x), v[0], v[1], v[2], v[3],
+                            &gw->nlong);
     for (int q = 0; q < 4; q++) {
         const double x = wave_max_d(v[q]);
         if (lane_id() == 0) red[q][wave_id()] = x;
@@ -370,6 +373,10 @@ __global__ void __launch_bounds__(1024) k_stats_tail_b(DevLU *Ds, FinishOut *Os,
     double v[4] = {0.0, 0.0, 0.0, 0.0};
     if (threadIdx.x < TAIL_BLOCKS)
         for (int q = 0; q < 4; q++) v[q] = ((const double *)gw->partll[0])[4 * threadIdx.x + q];
+    // the rows of more than 256 entries k_stats_tail_a recorded, on four waves
+    const int nlong = gw->nlong;
+    if (nlong && wave_id() < 4)
+        v[3] = fmax(v[3], stats_long_rows(D.bt_ptr, D.bt_idx, D.bt_val, D.qinv, D.pinv, D.gwork, D.m, S->rank, nlong, wave_id(), 4));
     __syncthreads();
     stats_tail_finish(D, red, chain_out, v[0], v[1], v[2], v[3]);
     // restore the all-zero invariant of the pivot_any work area

@@ -11,9 +11,9 @@
 //
 // Floating point: every sum is taken in the reference's order -- dots over a line in its storage order
 // (lane order of wave_ordered_sum), scatter updates of one entry in ascending pivot order, the residual
-// terms of a row ascending in the pivot position of their columns, the 1-norms sequentially over the row
-// indices -- so all statistics, including residual_test (pure rounding noise), are bit-identical to it
-// (tests: test_statistics_tail*).
+// terms of a row ascending in the pivot position of their columns (rows of every length: stats_long_rows takes
+// those of more than 256 entries), the 1-norms sequentially over the row indices -- so all statistics, including
+// residual_test (pure rounding noise), are bit-identical to it (tests: test_statistics_tail*, test_gpu_stats_rows.py).
 #include "blu_dev.h"
 
 #include "k_sweep.h"
@@ -76,10 +76,72 @@ __device__ __forceinline__ void forward_row_reg(const DevG &D, gdouble_p lf, int
     }
 }
 
+// The forward residual and row sum of the rows of more than 256 entries, which stats_tail_loops leaves to this pass (their
+// indices in gwork column 6, `nlong` of them): one wave per row, wave `slot` of `nslot` takes rows slot, slot + nslot, ...
+// The wave scatters the storage index of every pivotal entry of the row to a dense array indexed by pivot position (its
+// own slot of m ints in gwork columns 0-1, the condest work vectors, dead by now), then reads that array in position order,
+// 64 positions at a time, and applies the terms it finds one after the other (v_readlane): ascending in the pivot position
+// of their columns, as the reference does.  O(n + span of the positions / 64) per row of n entries.  The slots are never
+// cleared: an index p read back at position k counts only if p lies in the row and its column has position k.
+__device__ __forceinline__ double stats_long_rows(gcint_p bt_ptr, gcint_p bt_idx, gcdouble_p bt_val, gcint_p qinv, gcint_p pinv,
+                                                  gdouble_p gwork, int m, int rank, int nlong, int slot, int nslot)
+{
+    double inf = 0.0; // (the largest row sum of these rows; returned)
+    const int lane = lane_id();
+    gdouble_p lf = gwork + 2 * (size_t)(m + 1), rf = gwork + 3 * (size_t)(m + 1);
+    gcint_p list = (gcint_p)(gwork + 6 * (size_t)(m + 1));
+    gint_p pos = (gint_p)gwork + (size_t)slot * (m + 1); // (4 slots of m ints in 2 (m + 1) doubles)
+    for (int r = slot; r < nlong; r += nslot) {
+        const int i = list[r];
+        const int b = bt_ptr[i], e = bt_ptr[i + 1];
+        int lo = 0x7fffffff, hi = -1;
+        for (int p = b + lane; p < e; p += 64) {
+            const int kc = qinv[bt_idx[p]];
+            if (kc < rank) { // (entries in non-pivotal columns are skipped, as in the short paths)
+                pos[kc] = p;
+                lo = min(lo, kc);
+                hi = max(hi, kc);
+            }
+        }
+        lo = wave_min_i(lo);
+        hi = wave_max_i(hi);
+        wave_mem_sync(); // (one lane's stores before another lane's loads)
+        const int kr = pinv[i];
+        double acc = rf[kr], rsum = 0.0;
+        for (int k0 = lo; k0 <= hi; k0 += 64) {
+            const int k = k0 + lane;
+            double a = 0.0, t = 0.0;
+            bool hit = false;
+            if (k <= hi) {
+                const int p = pos[k];
+                if (p >= b && p < e && qinv[bt_idx[p]] == k) {
+                    a = bt_val[p];
+                    t = __dmul_rn(lf[k], a);
+                    hit = true;
+                }
+            }
+            for (unsigned long long bal = __ballot(hit); bal; bal &= bal - 1) {
+                const int src = __ffsll((long long)bal) - 1;
+                acc = __dsub_rn(acc, wave_bcast_d(t, src));
+                rsum += fabs(wave_bcast_d(a, src));
+            }
+        }
+        if (kr >= rank) {
+            acc = acc - lf[kr];
+            rsum += 1.0;
+        }
+        if (lane == 0) rf[kr] = acc;
+        inf = fmax(inf, rsum);
+        wave_mem_sync(); // (this row's loads of pos before the next row's stores)
+    }
+    return inf;
+}
+
 // REG: rows of at most 32 entries by forward_row_reg (the 256-thread workgroups of k_stats_tail: their register budget allows it)
+// nlong: counter of the rows of more than 256 entries, which are only recorded here (stats_long_rows); zero on entry
 template <bool REG>
 __device__ __forceinline__ void stats_tail_loops(const DevG &D, const FinishOut &O, int tid, int nt, double &nl, double &nu, double &one,
-                                                 double &inf)
+                                                 double &inf, int *nlong)
 {
     Scalars *S = D.s;
     const int m = D.m;
@@ -120,17 +182,23 @@ __device__ __forceinline__ void stats_tail_loops(const DevG &D, const FinishOut 
     // forward residual rhs - B*lhs and row sums: one thread per ROW of B (bt_* = B row-wise).  The
     // reference scatters column after column in pivot order (residual_test.rs:68-76, matrix_norm.rs:
     // 26-36), so a row receives its terms ascending in the pivot position of their columns: the entries
-    // of the row are taken in that order (selection by repeated minimum; rows are short).
+    // of the row are taken in that order (selection by repeated minimum up to 256 entries; longer rows are recorded
+    // for stats_long_rows, which sorts them by position).
     inf = 0.0;
+    gint_p longlist = (gint_p)(D.gwork + 6 * (size_t)(m + 1));
     for (int i = tid; i < m; i += nt) {
+        const int b = D.bt_ptr[i], e = D.bt_ptr[i + 1];
+        if (e - b > 256) {
+            longlist[atomicAdd(nlong, 1)] = i;
+            continue;
+        }
         const int kr = D.pinv[i];
         double acc = rf[kr], rsum = 0.0;
-        const int b = D.bt_ptr[i], e = D.bt_ptr[i + 1];
         if (REG && e - b <= 16) {
             forward_row_reg<16>(D, lf, b, e - b, rank, acc, rsum);
         } else if (REG && e - b <= 32) {
             forward_row_reg<32>(D, lf, b, e - b, rank, acc, rsum);
-        } else if (e - b <= 256) {
+        } else {
             int last = -1;
             for (int t = b; t < e; t++) {
                 int best = 0x7fffffff, bp = -1;
@@ -146,15 +214,6 @@ __device__ __forceinline__ void stats_tail_loops(const DevG &D, const FinishOut 
                 acc = __dsub_rn(acc, __dmul_rn(lf[best], a));
                 rsum += fabs(a);
                 last = best;
-            }
-        } else { // a very long row: storage order (the sums then agree with the reference to rounding only)
-            for (int p = b; p < e; p++) {
-                const int kc = D.qinv[D.bt_idx[p]];
-                if (kc < rank) {
-                    const double a = D.bt_val[p];
-                    acc = __dsub_rn(acc, __dmul_rn(lf[kc], a));
-                    rsum += fabs(a);
-                }
             }
         }
         if (kr >= rank) {
@@ -217,11 +276,24 @@ __device__ __forceinline__ void stats_tail_finish(const DevG &D, double (*red)[4
         S->residual_test = fmax(nrf / ((double)m + chain_out[10] * nf), nrb / ((double)m + chain_out[11] * nb));
     }
 }
-template <bool REG> __device__ __forceinline__ void stats_tail(const DevG &D, const FinishOut &O, double (*red)[40], double *chain_out)
+// the long rows of a workgroup's matrix (nlong: an LDS counter, zeroed before the workgroup's barrier ahead of this) on
+// up to four of its waves, between the per-thread passes and the final numbers
+__device__ __forceinline__ void stats_tail_long_rows(const DevG &D, int nlong, double &inf)
+{
+    const int nslot = num_waves() < 4 ? num_waves() : 4;
+    if (wave_id() < nslot)
+        inf = fmax(inf, stats_long_rows(D.bt_ptr, D.bt_idx, D.bt_val, D.qinv, D.pinv, D.gwork, D.m, D.s->rank, nlong, wave_id(), nslot));
+}
+template <bool REG> __device__ __forceinline__ void stats_tail(const DevG &D, const FinishOut &O, double (*red)[40], double *chain_out, int *nlong)
 {
     double nl, nu, one, inf;
-    stats_tail_loops<REG>(D, O, threadIdx.x, blockDim.x, nl, nu, one, inf);
+    stats_tail_loops<REG>(D, O, threadIdx.x, blockDim.x, nl, nu, one, inf, nlong);
     __syncthreads();
+    const int nl256 = *nlong;
+    if (nl256) { // (uniform)
+        stats_tail_long_rows(D, nl256, inf);
+        __syncthreads();
+    }
     stats_tail_finish(D, red, chain_out, nl, nu, one, inf);
 }
 
@@ -233,9 +305,11 @@ __global__ void __launch_bounds__(1024) k_stats(DevLU *Ds, FinishOut *Os, int do
     Scalars *S = D.s;
     __shared__ double red[4][40];
     __shared__ double chain_out[16];
+    __shared__ int nlong;
     const int tid = threadIdx.x, nt = blockDim.x, w = wave_id(), lane = lane_id(), nw = num_waves();
     const int m = D.m;
     if (S->status != ST_DONE || D.skip_stats) return;
+    if (tid == 0) nlong = 0;
     const int rank = S->rank;
     // six m-vectors in the (all-zero) pivot_any work area; re-zeroed at the end
     gdouble_p wl = D.gwork, wu = D.gwork + (size_t)(m + 1), lf = D.gwork + 2 * (size_t)(m + 1),
@@ -344,7 +418,7 @@ __global__ void __launch_bounds__(1024) k_stats(DevLU *Ds, FinishOut *Os, int do
         }
         return;
     }
-    stats_tail<false>(D, O, red, chain_out);
+    stats_tail<false>(D, O, red, chain_out, &nlong);
     // restore the all-zero invariant of the pivot_any work area
     const size_t ng = (size_t)7 * (m + 1);
     for (size_t e = tid; e < ng; e += nt) D.gwork[e] = 0.0;
@@ -357,6 +431,7 @@ template <int NT> __global__ void __launch_bounds__(NT) k_stats_tail(DevLU *Ds, 
 {
     __shared__ double red[4][40];
     __shared__ double chain_out[16];
+    __shared__ int nlong;
     for (int b = blockIdx.x; b < nmat; b += gridDim.x) {
         const DevG D(Ds[b]);
         Scalars *S = D.s;
@@ -364,9 +439,10 @@ template <int NT> __global__ void __launch_bounds__(NT) k_stats_tail(DevLU *Ds, 
             if (threadIdx.x == 0) {
                 chain_out[0] = S->normest_l_inv;
                 chain_out[1] = S->normest_u_inv;
+                nlong = 0;
             }
             __syncthreads();
-            stats_tail<NT <= 512>(D, Os[b], red, chain_out);
+            stats_tail<NT <= 512>(D, Os[b], red, chain_out, &nlong);
             const size_t ng = (size_t)7 * (D.m + 1);
             for (size_t e = threadIdx.x; e < ng; e += blockDim.x) D.gwork[e] = 0.0;
         }

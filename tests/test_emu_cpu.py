@@ -134,3 +134,43 @@ def test_step_check_of_the_line_records_on_the_cpu(emu_lib):
         out = subprocess.run([sys.executable, os.path.join(ROOT, "tools", "gpu_stepcheck.py"), "160,7,8,0.5,0.3,3", "--step", "25"] + extra,
                              env=env, capture_output=True, text=True, timeout=900)
         assert out.returncode == 0 and "FACTORS IDENTICAL" in out.stdout and "MISMATCH" not in out.stdout, out.stdout[-2500:] + out.stderr[-2500:]
+
+
+CHILD_STATS = r"""
+import sys, numpy as np
+sys.path.insert(0, %(root)r)
+import blu_amd
+from blu_amd import keys as K
+from oracle import orc
+from tests import util
+assert b"gfx950" in blu_amd.lib().blu_hip_version()
+cases = [util.long_row_case(orc, %(m)d, rowlen, 1) for rowlen in %(rowlens)r]
+mats = [mat for _, mat, _, _ in cases]
+hs = [blu_amd.BLU(len(cp) - 1, len(ri)) for cp, ri, v in mats]
+if %(batch)r:
+    st = blu_amd.factorize_batch(hs, mats)
+else:
+    st = [h.factorize(cp[:-1], cp[1:], ri, v) for h, (cp, ri, v) in zip(hs, mats)]
+for g, (seed, (cp, ri, v), o, so), s in zip(hs, cases, st):
+    assert s == so == K.OK, (seed, s, so)
+    util.assert_same_factors(g.get_factors(), o.get_factors(), rtol=0.0)
+    for c in ("NORM_L", "NORM_U", "ONENORM", "INFNORM"):
+        a, b = g.stat(getattr(K, "STAT_" + c)), o.stat(getattr(K, "STAT_" + c))
+        assert a == b, (len(cp) - 1, int(np.bincount(ri.astype(np.int64)).max()), seed, c, a, b)
+print("STATS OK")
+"""
+
+
+@pytest.mark.parametrize("batch", [True, False], ids=["batch", "single"])
+def test_norms_of_rows_of_every_length_on_the_cpu(emu_lib, batch):
+    """The matrix norms of the statistics tail on bases with one row of 17, 33, 257 and 590 entries (util.long_row_case:
+    bases on which summing that row in storage order instead of the pivot order of its columns changes INFNORM): the
+    short-row paths and the long-row pass of k_stats.hip, as a batch (k_stats + k_stats_tail<512>) and one basis at a
+    time (k_stats with the tail; BLU_PIVOT_KERNEL=1, as the default single-basis pivot kernel is not emulated).
+    Only NORM_L, NORM_U, ONENORM and INFNORM are compared: the triangular sweeps of k_stats (condest, residual_test) and
+    solve_dense are not validated under the emulator, so the condition estimates, the residual and
+    the solves are left to the GPU suite (tests/test_gpu_stats_rows.py)."""
+    code = CHILD_STATS % {"root": ROOT, "m": 600, "rowlens": [17, 33, 257, 590], "batch": batch}
+    env = dict(os.environ, BLU_HIP_LIB=emu_lib, BLU_PIVOT_KERNEL="0" if batch else "1")
+    out = subprocess.run([sys.executable, "-c", code], env=env, capture_output=True, text=True, timeout=600)
+    assert out.returncode == 0 and "STATS OK" in out.stdout, out.stdout[-2000:] + out.stderr[-4000:]

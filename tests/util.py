@@ -94,3 +94,77 @@ def oracle_factorize(orc, cp, ri, v, params=None, cap=None, allow_d3=False):
         return o, st
     assert allow_d3, "reference defect D3 would be hit (%d times): choose another matrix or pass allow_d3" % o.d3_hits()
     return o, st
+
+
+def basis_with_long_row(m, rowlen, seed, singular=False):
+    """gen_lp_basis(m, 6, 8, 0.5, seed, 0.3) with row m // 2 filled to exactly `rowlen` entries in random columns,
+    |values| = U(0.1, 1) * 10^U(-6, 2) with random signs, so that this row has the largest sum of |a|.
+    singular: three columns holding an entry of that row are scaled by 1e-17, so rank < m and the long row has entries
+    in columns that do not become pivotal.  Returns (colptr, rowidx, values) with the rows of a column ascending."""
+    from oracle import orc
+    cp, ri, v = orc.gen_lp_basis(m, 6, 8, 0.5, seed, 0.3)
+    r = m // 2
+    rng = np.random.default_rng(7919 * seed + rowlen)
+    cols = [dict(zip(ri[cp[j]:cp[j + 1]].astype(np.int64).tolist(), v[cp[j]:cp[j + 1]].tolist())) for j in range(m)]
+    have = [j for j in range(m) if r in cols[j]]
+    assert len(have) <= rowlen, (len(have), rowlen)
+    free = np.array([j for j in range(m) if r not in cols[j]], np.int64)
+    for j in rng.choice(free, rowlen - len(have), replace=False):
+        cols[int(j)][r] = float(rng.choice((-1.0, 1.0)) * rng.uniform(0.1, 1.0) * 10.0 ** rng.uniform(-6.0, 2.0))
+    if singular:
+        inrow = [j for j in range(m) if r in cols[j]]
+        for j in rng.choice(inrow, 3, replace=False):
+            cols[int(j)] = {i: x * 1e-17 for i, x in cols[int(j)].items()}
+    ncp, nri, nv = [0], [], []
+    for j in range(m):
+        for i in sorted(cols[j]):
+            nri.append(i)
+            nv.append(cols[j][i])
+        ncp.append(len(nri))
+    return np.array(ncp, np.uint64), np.array(nri, np.uint64), np.array(nv)
+
+
+def row_sums_two_orders(cp, ri, v, row, f, rank):
+    """Sum of |a| over the entries of `row` in pivotal columns (colperm[0..rank)), plus 1 if the row itself is not pivotal
+    (the unit column that replaces a dependent one), added sequentially in two orders: ascending column index (the order
+    in which the row is stored) and ascending pivot position of the column (the reference's order, matrix_norm.rs).
+    Returns (storage_order_sum, pivot_order_sum)."""
+    m = len(cp) - 1
+    cols = np.repeat(np.arange(m), np.diff(cp.astype(np.int64)))
+    mask = ri.astype(np.int64) == row
+    c, a = cols[mask], np.asarray(v)[mask]
+    qinv = np.empty(m, np.int64)
+    qinv[np.asarray(f["colperm"], np.int64)] = np.arange(m)
+    pinv = np.empty(m, np.int64)
+    pinv[np.asarray(f["rowperm"], np.int64)] = np.arange(m)
+    keep = qinv[c] < rank
+    c, a = c[keep], a[keep]
+    sums = []
+    for order in (np.argsort(c, kind="stable"), np.argsort(qinv[c], kind="stable")):
+        s = 0.0
+        for x in a[order]:
+            s += abs(float(x))
+        if pinv[row] >= rank:
+            s += 1.0
+        sums.append(s)
+    return sums[0], sums[1]
+
+
+def long_row_case(orc, m, rowlen, seed, singular=False, tries=60):
+    """The first seed from `seed` on whose basis_with_long_row the two summation orders of row_sums_two_orders give
+    different sums, that row has the largest sum of |a|, and the faithful oracle does not meet reference defect D3:
+    a basis on which the statistics of a kernel that summed the long row in storage order would differ from the
+    reference.  Returns (seed, (cp, ri, v), oracle handle, oracle status)."""
+    for s in range(seed, seed + tries):
+        cp, ri, v = basis_with_long_row(m, rowlen, s, singular)
+        o, so = oracle_factorize(orc, cp, ri, v, allow_d3=True)
+        if o.d3_hits() or so not in (K.OK, K.WARNING_SINGULAR_MATRIX):
+            continue
+        rank = int(o.stat(K.STAT_RANK))
+        assert (rank < m) == singular, (rank, m)
+        f = o.get_factors()
+        a, b = row_sums_two_orders(cp, ri, v, m // 2, f, rank)
+        rows = np.bincount(ri.astype(np.int64), weights=np.abs(v), minlength=m)
+        if a != b and b == o.stat(K.STAT_INFNORM) and np.argmax(rows) == m // 2:
+            return s, (cp, ri, v), o, so
+    raise AssertionError("no seed in [%d, %d) separates the two orders of row %d (m %d, %d entries)" % (seed, seed + tries, m // 2, m, rowlen))
