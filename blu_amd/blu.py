@@ -119,7 +119,9 @@ def gen_lp_basis(m, k, bw, tri_frac, seed, offscale=1.0):
 def factorize_batch(handles, mats=None, device_ptrs=None, block=None):
     """Factorize len(handles) independent bases concurrently on one GPU (one workgroup per basis).
 
-    mats: list of (colptr, rowidx, values) host CSC triples, or
+    mats: list of host matrices, each a CSC triple (colptr, rowidx, values) or, as BLU.factorize takes it, a quadruple
+    (b_begin, b_end, b_i, b_x): column j is b_i[b_begin[j]..b_end[j]), b_x[...] (columns gathered from a larger
+    matrix, in any order and with gaps between them), or
     device_ptrs: list of (p_begin, p_end, p_i, p_x, nnz_len) raw device pointers (inputs already in HBM).
     Returns the list of per-handle statuses (reference Status numbering)."""
     n = len(handles)
@@ -138,12 +140,22 @@ def factorize_batch(handles, mats=None, device_ptrs=None, block=None):
             pb[k], pe[k], pi[k], px[k], ln[k] = b, e, i, x, int(nn)
         on_dev = 1
     else:
-        for k, (cp, ri, v) in enumerate(mats):
-            cp = np.ascontiguousarray(cp, dtype=np.uint64)
+        for k, mat in enumerate(mats):
+            if len(mat) == 3:
+                cp, ri, v = mat
+                cp = np.ascontiguousarray(cp, dtype=np.uint64)
+                bb, be = cp[:-1], cp[1:]
+            else:
+                bb, be, ri, v = mat
+                bb = np.ascontiguousarray(bb, dtype=np.uint64)
+                be = np.ascontiguousarray(be, dtype=np.uint64)
+                cp = None
+                if len(bb) != handles[k].m or len(be) != handles[k].m or len(ri) != len(v):
+                    raise ValueError("factorize_batch: member %d: b_begin / b_end need m entries, b_i / b_x equal lengths" % k)
             ri = np.ascontiguousarray(ri, dtype=np.uint64)
             v = np.ascontiguousarray(v, dtype=np.float64)
-            keep.append((cp, ri, v))
-            pb[k], pe[k], pi[k], px[k], ln[k] = cp.ctypes.data, cp.ctypes.data + 8, ri.ctypes.data, v.ctypes.data, len(ri)
+            keep.append((cp, bb, be, ri, v))
+            pb[k], pe[k], pi[k], px[k], ln[k] = bb.ctypes.data, be.ctypes.data, ri.ctypes.data, v.ctypes.data, len(ri)
         on_dev = 0
     UNTOUCHED = -12345
     st = (C.c_int * n)(*([UNTOUCHED] * n))

@@ -222,6 +222,29 @@ static int oom_or_device(blu_hip *h)
 {
     return h->err.find("hipMalloc") != std::string::npos ? BLU_ERROR_OUT_OF_MEMORY : BLU_ERROR_DEVICE;
 }
+// lu.reset() (lu.rs:329-359), the first thing every factorize call does (factorize.rs:44-47) whatever it returns: the
+// statistics of the last factorization and of its updates read as a fresh LU's until this factorize succeeds.  (The
+// device diagnostics of the last call stay: exit status and source line, statistics 57 / 58; fill paths, 119.)
+static void reset_lu(blu_hip *h)
+{
+    const int status = h->hs.status, err_line = h->hs.err_line, fill_paths = h->hs.fill_paths;
+    memset(&h->hs, 0, sizeof(Scalars));
+    h->hs.status = status;
+    h->hs.err_line = err_line;
+    h->hs.fill_paths = fill_paths;
+    h->nupdate = -1;               // invalidate the factorization (lu.rs:331)
+    h->update_cost_denom = 1.0;    // (lu.rs:340)
+    h->sp_l_flops = h->sp_u_flops = 0;
+    h->upd_for_nfact = -1;         // nforrest, pivot_error, r_nz, r_flops, max_eta, update_cost_numer: 0 (lu.rs:332-346)
+    h->lt_for_nfact = h->rows_for_nfact = -1; // row-wise copies of the old factors: never to be used again
+}
+// lu.update_cost_denom of a factorization that succeeded (factorize.rs:160-166)
+static void set_factor_cost(blu_hip *h)
+{
+    const Scalars &s = h->hs;
+    h->update_cost_denom = 250.0 * (0.04 * (double)h->m + 0.07 * (double)s.matrix_nz + 0.20 * (double)s.bump_nz +
+                                    0.20 * (double)s.nsearch_pivot + 0.008 * (double)s.factor_flops);
+}
 
 // ---- phase 3+4: pivot loop (relaunched until every handle is done / stopped / failed), then read-out
 // Workgroups of the O(nnz) kernels of a batch (k_prep, k_setup, k_finish: one workgroup works on one matrix at a time and
@@ -448,6 +471,7 @@ static bool batch_pivot_and_finish(BatchCtx &B)
         }
         h->nupdate = 0; // factorization successfully finished (factorize.rs:114-119)
         h->nfactorize++;
+        set_factor_cost(h);
         if (rows_built_for == h) h->lt_for_nfact = h->rows_for_nfact = h->nfactorize; // the row-wise copies belong to THIS factorization
         B.result[k] = h->hs.rank < h->m ? BLU_WARNING_SINGULAR_MATRIX : BLU_OK;
     }
@@ -599,9 +623,13 @@ static int factorize_batch_impl(blu_hip **hs, int n, const uint64_t *const *d_b_
             for (int k = 0; k < n; k++) status[k] = code;
         return code;
     };
+    for (int k = 0; k < n; k++)
+        if (!hs[k]) return fail_all(BLU_ERROR_INVALID_ARGUMENT);
+    // the factors every handle holds are invalid from here on, whatever happens next
+    for (int k = 0; k < n; k++) reset_lu(hs[k]);
     if (hipSetDevice(h0->device) != hipSuccess) return fail_all(BLU_ERROR_DEVICE);
     for (int k = 0; k < n; k++)
-        if (!hs[k] || hs[k]->device != h0->device) return fail_all(BLU_ERROR_INVALID_ARGUMENT);
+        if (hs[k]->device != h0->device) return fail_all(BLU_ERROR_INVALID_ARGUMENT);
     if (n > 1) { // the same handle twice = two workgroups on one DevLU: rejected
         std::vector<blu_hip *> sorted(hs, hs + n);
         std::sort(sorted.begin(), sorted.end());
@@ -609,11 +637,6 @@ static int factorize_batch_impl(blu_hip **hs, int n, const uint64_t *const *d_b_
     }
     for (int k = 0; k < n; k++)
         if (b_i_len[k] > (uint64_t)kIntMax) return fail_all(BLU_ERROR_INVALID_ARGUMENT); // 32-bit device indices
-    // the factors every handle holds are invalid from here on, whatever happens next (lu.reset(), lu.rs:331)
-    for (int k = 0; k < n; k++) {
-        hs[k]->nupdate = -1;
-        hs[k]->lt_for_nfact = hs[k]->rows_for_nfact = -1; // row-wise copies of the old factors: never to be used again
-    }
     BatchCtx B;
     if (!batch_init(B, hs, n)) {
         batch_release(B);
@@ -623,8 +646,6 @@ static int factorize_batch_impl(blu_hip **hs, int n, const uint64_t *const *d_b_
         blu_hip *h = hs[k];
         DevLU &D = h->D;
         h->err.clear();
-        h->nupdate = -1; // lu.reset(): invalidate (lu.rs:331)
-        h->sp_l_flops = h->sp_u_flops = 0;
         D.b_begin = (const unsigned long long *)d_b_begin[k];
         D.b_end = (const unsigned long long *)d_b_end[k];
         D.b_i = (const unsigned long long *)d_b_i[k];
@@ -634,6 +655,7 @@ static int factorize_batch_impl(blu_hip **hs, int n, const uint64_t *const *d_b_
             memset(&h->hs, 0, sizeof(Scalars));
             h->nupdate = 0;
             h->nfactorize++;
+            set_factor_cost(h);
             B.result[k] = BLU_OK;
         }
     }
@@ -646,6 +668,7 @@ static int factorize_batch_impl(blu_hip **hs, int n, const uint64_t *const *d_b_
     for (int k = 0; k < n; k++) {
         int r = B.result[k];
         if (r == kPending) r = BLU_ERROR_DEVICE;
+        if (r < 0) reset_lu(hs[k]); // what the kernels counted before they refused B is not the reference's: it counts nothing (singletons.rs:119-259)
         if (status) status[k] = r;
         if (r < 0) worst_err = std::min(worst_err, r);
         else worst_pos = std::max(worst_pos, r);

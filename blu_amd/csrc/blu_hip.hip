@@ -67,6 +67,7 @@ struct blu_hip {
     // state
     int64_t nupdate;   // -1 = None
     int64_t nfactorize;
+    double update_cost_denom; // lu.update_cost_denom: 1 from the start of a factorize, the factor cost once it succeeded (factorize.rs:160-166)
     DevLU D;           // host copy of the device descriptor (device pointers inside)
     char *slab;        // one allocation holding every fixed-size device array of this handle
     DevLU *dD;         // device copy (own slot)
@@ -254,6 +255,7 @@ extern "C" blu_hip *blu_hip_new(int64_t m, int64_t b_nz, int device)
     h->realloc_factor = 1.5;
     h->nupdate = -1;
     h->nfactorize = 0;
+    h->update_cost_denom = 0.0; // (LU::new: Default, lu.rs:261-318)
     memset(&h->sw, 0, sizeof(SparseWs));
     h->sw_ready = false;
     h->sw_ltcap = 0;
@@ -495,9 +497,7 @@ extern "C" double blu_hip_get_stat(const blu_hip *h, int key)
         for (int k = 0; k < 4; k++) tot += (double)s.prof[k];
         return tot > 0.0 ? h->t_pivot * (1.0 - (double)s.prof[0] / tot) : h->t_pivot;
     }
-    case BLU_STAT_UPDATE_COST_DENOM: // factorize.rs:160-166
-        return 250.0 * (0.04 * (double)h->m + 0.07 * (double)s.matrix_nz + 0.20 * (double)s.bump_nz +
-                        0.20 * (double)s.nsearch_pivot + 0.008 * (double)s.factor_flops);
+    case BLU_STAT_UPDATE_COST_DENOM: return h->update_cost_denom;
     case BLU_STAT_RANKDEF: return (double)s.rankdef;
     case BLU_STAT_L_MEM: return (double)h->D.lcap;
     case BLU_STAT_U_MEM: return (double)h->D.ucap;
@@ -868,7 +868,10 @@ extern "C" int blu_hip_solve_dense(blu_hip *h, const double *rhs, double *lhs, c
     if (h->m == 0) return BLU_OK;
     if (hipSetDevice(h->device) != hipSuccess) return BLU_ERROR_DEVICE;
     const size_t M = (size_t)h->m;
-    if (!h->d_rhs && (!dalloc(h, &h->d_rhs, M) || !dalloc(h, &h->d_lhs, M))) return BLU_ERROR_OUT_OF_MEMORY;
+    if (!h->d_rhs || !h->d_lhs) { // (both or neither: a failed allocation of the second leaves none)
+        dfree(h->d_rhs); dfree(h->d_lhs);
+        if (!dalloc(h, &h->d_rhs, M) || !dalloc(h, &h->d_lhs, M)) return BLU_ERROR_OUT_OF_MEMORY;
+    }
     if (!hip_ok(h, hipMemcpy(h->d_rhs, rhs, M * 8, hipMemcpyHostToDevice), "h2d rhs")) return BLU_ERROR_DEVICE;
     const int tr = (trans == 't' || trans == 'T') ? 1 : 0;
     if (h->nupdate > 0) { // updated factorization: mutable U, row etas, pivot sequence (k_update.hip)

@@ -62,9 +62,15 @@ static int ensure_upd(blu_hip *h)
         if (!dalloc(h, &U.ridx, (size_t)rneed) || !dalloc(h, &U.rval, (size_t)rneed)) return BLU_ERROR_OUT_OF_MEMORY;
         U.rcapacity = (int)rneed;
     }
+    // the totals count over the life of the handle: LU::reset leaves them (lu.rs:329-359), k_upd_init starts from zero
+    const long long nsymperm_total = h->ust.nsymperm_total, nunsymperm_total = h->ust.nunsymperm_total, nforrest_total = h->ust.nforrest_total;
     hipLaunchKernelGGL(k_upd_init, dim3(1), dim3(1024), 0, h->stream, h->dD, h->dO, U);
     if (!hip_ok(h, hipStreamSynchronize(h->stream), "k_upd_init")) return BLU_ERROR_DEVICE;
     if (!download_upd(h)) return BLU_ERROR_DEVICE;
+    h->ust.nsymperm_total = nsymperm_total;
+    h->ust.nunsymperm_total = nunsymperm_total;
+    h->ust.nforrest_total = nforrest_total;
+    if (!hip_ok(h, hipMemcpy(U.st, &h->ust, sizeof(UpdState), hipMemcpyHostToDevice), "h2d update state")) return BLU_ERROR_DEVICE;
     h->upd_for_nfact = h->nfactorize;
     return BLU_OK;
 }

@@ -174,3 +174,80 @@ def test_norms_of_rows_of_every_length_on_the_cpu(emu_lib, batch):
     env = dict(os.environ, BLU_HIP_LIB=emu_lib, BLU_PIVOT_KERNEL="0" if batch else "1")
     out = subprocess.run([sys.executable, "-c", code], env=env, capture_output=True, text=True, timeout=600)
     assert out.returncode == 0 and "STATS OK" in out.stdout, out.stdout[-2000:] + out.stderr[-4000:]
+
+
+CHILD_SEQ = r"""
+import sys, numpy as np
+sys.path.insert(0, %(root)r)
+import blu_amd
+from blu_amd import keys as K
+from oracle import orc
+from tests import util
+assert b"gfx950" in blu_amd.lib().blu_hip_version()
+# what the emulator validates of a factorize that succeeded (DESIGN.md section 4b): the counters, the pivots, the matrix
+# norms and what derives from them; after a refused factorize every getter is compared
+EMU_STATS = ("M", "NUPDATE", "NFACTORIZE", "L_NZ", "U_NZ", "MIN_PIVOT", "MAX_PIVOT", "NORM_L", "NORM_U", "ONENORM", "INFNORM",
+             "MATRIX_NZ", "RANK", "BUMP_SIZE", "BUMP_NZ", "NSEARCH_PIVOT", "FACTOR_FLOPS", "UPDATE_COST_DENOM", "RANKDEF",
+             "L_FLOPS", "U_FLOPS", "NFORREST", "R_NZ", "UPDATE_COST")
+ms = %(ms)r
+batch = %(batch)r
+
+def step_input(kind, m, seed):
+    if kind == "csc":
+        cp, ri, v = orc.gen_lp_basis(m, 6, 8, 0.5, seed, 0.3)
+        return (cp, ri, v), (cp[:-1], cp[1:], ri, v)
+    if kind == "plain":
+        q = util.gathered_basis(m, seed)
+    elif kind == "twice":
+        q = util.gathered_basis(m, seed, twice=True)
+    elif kind == "empty_last":
+        q = util.gathered_basis(m, seed, n_empty=2, end_last=True)
+    else:
+        q = util.spoil(*util.gathered_basis(m, seed), kind, seed)
+    return q, q
+
+kinds = ["plain", "index", "twice", "order", "empty_last", "csc", "plain"]
+hs = [blu_amd.BLU(m, 4 * m) for m in ms]
+os_ = [orc.OracleBLU(m, 400 * m) for m in ms]
+for o in os_:
+    o.set_fix_d3(True)
+for s in range(len(kinds)):
+    steps = [kinds[(s + k) %% len(kinds)] for k in range(len(ms))]  # the members of a batch take different kinds
+    ins = [step_input(kind, m, 10 * s + k) for k, (kind, m) in enumerate(zip(steps, ms))]
+    if batch:
+        st = blu_amd.factorize_batch(hs, [a for a, _ in ins])
+    else:
+        st = [h.factorize(*q) for h, (_, q) in zip(hs, ins)]
+    for k, (h, o, (_, q), kind, m) in enumerate(zip(hs, os_, ins, steps, ms)):
+        where = (s, k, kind)
+        so = o.factorize(*q)
+        assert st[k] == so, (where, st[k], so)
+        assert st[k] == {"index": K.ERROR_INVALID_ARGUMENT, "order": K.ERROR_INVALID_ARGUMENT, "twice": K.WARNING_SINGULAR_MATRIX,
+                         "empty_last": K.WARNING_SINGULAR_MATRIX}.get(kind, K.OK), where
+        if st[k] < 0:
+            util.assert_same_getters(h, o, where)
+            assert util.status_of(h.get_factors) == util.status_of(o.get_factors) == K.ERROR_INVALID_CALL, where
+            continue
+        f = h.get_factors()
+        util.assert_same_factors(f, o.get_factors(), rtol=0.0)
+        rank = int(h.stat(K.STAT_RANK))
+        util.check_factors(*util.gathered_csc(*q, m), f, rank=rank)
+        for c in EMU_STATS:
+            a, b = h.stat(getattr(K, "STAT_" + c)), o.stat(getattr(K, "STAT_" + c))
+            assert a == b, (where, c, a, b)
+print("SEQ OK")
+"""
+
+
+@pytest.mark.parametrize("batch", [False, True], ids=["single", "batch"])
+def test_gathered_bases_and_refused_calls_on_the_cpu(emu_lib, batch):
+    """The call pattern of a simplex code, factorize part: on the same handles, bases gathered from a larger matrix
+    (util.gathered_basis: columns out of storage order, poison between them, empty columns, a column listed twice, the
+    last column ending at len(b_i)), CSC bases, and B that factorize refuses (a row index >= m; b_end < b_begin).  Every
+    status, the canonical factors and the validated statistics equal the oracle's driven through the same sequence; after a
+    refused call every getter does (lu.reset(), lu.rs:329-359: MATRIX_NZ 0, UPDATE_COST_DENOM 1), and get_factors is an
+    invalid call.  Single bases with the one-wave kernel (BLU_PIVOT_KERNEL=1); a batch of three members of different m."""
+    code = CHILD_SEQ % {"root": ROOT, "ms": [300, 240, 300] if batch else [300], "batch": batch}
+    env = dict(os.environ, BLU_HIP_LIB=emu_lib, BLU_PIVOT_KERNEL="0" if batch else "1")
+    out = subprocess.run([sys.executable, "-c", code], env=env, capture_output=True, text=True, timeout=900)
+    assert out.returncode == 0 and "SEQ OK" in out.stdout, out.stdout[-2000:] + out.stderr[-4000:]

@@ -168,3 +168,149 @@ def long_row_case(orc, m, rowlen, seed, singular=False, tries=60):
         if a != b and b == o.stat(K.STAT_INFNORM) and np.argmax(rows) == m // 2:
             return s, (cp, ri, v), o, so
     raise AssertionError("no seed in [%d, %d) separates the two orders of row %d (m %d, %d entries)" % (seed, seed + tries, m // 2, m, rowlen))
+
+
+def gathered_basis(m, seed, k=6, bw=8, tri_frac=0.5, offscale=0.3, n_empty=0, twice=False, end_last=False, extra=None):
+    """B as a simplex code passes it: columns gathered from a constraint matrix A by b_begin = A_begin[basis],
+    b_end = A_end[basis], with b_i / b_x being A's whole arrays (include/blu_hip.h: blu_hip_factorize; the reference's
+    singletons.rs:119-198 reads B only through the [b_begin[j], b_end[j]) ranges).
+
+    A holds the gen_lp_basis(m, k, bw, tri_frac, seed, offscale) columns plus `extra` (default m) random columns of 1-5
+    entries, in shuffled storage order, the rows of every column shuffled.  Between two columns lie 0-3 poison entries:
+    row index >= m and a NaN value, so a kernel that reads outside a range returns ERROR_INVALID_ARGUMENT or a NaN
+    statistic.  The basis is the gen_lp_basis columns in a random order, except:
+      n_empty   that many basis columns are replaced by empty columns of A (begin == end; the basis is singular),
+      twice     one basis column is listed a second time in place of another: two columns share storage (singular),
+      end_last  the column stored last in A is a basis column and nothing follows it (b_end[j] == len(b_i)).
+    Returns (b_begin, b_end, b_i, b_x): uint64, uint64, uint64, float64."""
+    from oracle import orc
+    cp, ri, v = orc.gen_lp_basis(m, k, bw, tri_frac, seed, offscale)
+    rng = np.random.default_rng(104729 * seed + m)
+    cols = [(ri[cp[j]:cp[j + 1]].astype(np.int64), v[cp[j]:cp[j + 1]].copy()) for j in range(m)]
+    for _ in range(m if extra is None else extra):
+        n = int(rng.integers(1, 6))
+        cols.append((rng.choice(m, n, replace=False).astype(np.int64), rng.standard_normal(n)))
+    for _ in range(n_empty):
+        cols.append((np.zeros(0, np.int64), np.zeros(0)))
+    order = rng.permutation(len(cols))  # storage position -> column of A
+    if end_last:  # a basis column goes last
+        last = int(np.flatnonzero(order < m)[-1])
+        order[last], order[-1] = order[-1], order[last]
+    a_begin = np.zeros(len(cols), np.uint64)
+    a_end = np.zeros(len(cols), np.uint64)
+    b_i, b_x = [], []
+    for pos, c in enumerate(order):
+        gap = int(rng.integers(0, 4))
+        b_i += (m + rng.integers(0, 3 * m + 1, gap)).tolist()
+        b_x += [np.nan] * gap
+        idx, val = cols[int(c)]
+        perm = rng.permutation(len(idx))
+        a_begin[c] = len(b_i)
+        b_i += idx[perm].tolist()
+        b_x += val[perm].tolist()
+        a_end[c] = len(b_i)
+    if not end_last:  # poison after the last column too
+        b_i += [m, 2 * m + 7]
+        b_x += [np.nan, np.nan]
+    basis = rng.permutation(m)  # basis position -> column of A
+    if n_empty:
+        for p, c in zip(rng.choice(m, n_empty, replace=False), range(len(cols) - n_empty, len(cols))):
+            basis[p] = c
+    if twice:
+        p, q = rng.choice(m, 2, replace=False)
+        basis[q] = basis[p]
+    b_i, b_x = np.array(b_i, np.uint64), np.array(b_x, np.float64)
+    assert not end_last or a_end[order[-1]] == len(b_i)
+    return a_begin[basis].copy(), a_end[basis].copy(), b_i, b_x
+
+
+def gathered_matrix(b_begin, b_end, b_i, b_x, m):
+    """scipy CSC matrix assembled from the [b_begin[j], b_end[j]) ranges alone (nothing else of b_i / b_x is read)."""
+    idx, val, ptr = [], [], [0]
+    for j in range(m):
+        a, b = int(b_begin[j]), int(b_end[j])
+        idx.append(np.asarray(b_i[a:b], np.int64))
+        val.append(np.asarray(b_x[a:b], np.float64))
+        ptr.append(ptr[-1] + b - a)
+    B = sp.csc_matrix((np.concatenate(val), np.concatenate(idx), np.array(ptr, np.int64)), shape=(m, m))
+    B.sort_indices()
+    return B
+
+
+def gathered_csc(b_begin, b_end, b_i, b_x, m):
+    """(colptr, rowidx, values) of gathered_matrix, the form util.check_factors takes."""
+    B = gathered_matrix(b_begin, b_end, b_i, b_x, m)
+    return B.indptr.astype(np.uint64), B.indices.astype(np.uint64), B.data.copy()
+
+
+# Getters assert_same_getters leaves out, each for its reason.
+GETTERS_NOT_COMPARED = {
+    K.STAT_TIME_FACTORIZE: "wall-clock time",
+    K.STAT_TIME_SINGLETONS: "device time",
+    K.STAT_TIME_SEARCH_PIVOT: "device time",
+    K.STAT_TIME_ELIM_PIVOT: "device time",
+    K.STAT_L_MEM: "storage size: the device sizes its arenas its own way",
+    K.STAT_U_MEM: "storage size",
+    K.STAT_W_MEM: "storage size",
+    K.STAT_DEV_TIME_PIVOT_LOOP: "device diagnostic without a reference counterpart",
+    K.STAT_DEV_TIME_TOTAL: "device diagnostic",
+    K.STAT_DEV_RELAUNCHES: "device diagnostic",
+    K.STAT_NEXPAND: "counts line moves inside the file, so depends on the memory layout (include/blu_hip.h)",
+    K.STAT_NGARBAGE: "counts compressions of the file, so depends on the memory layout (include/blu_hip.h)",
+}
+# Getters blu_hip_set_skip_stats turns to 0 by contract (include/blu_hip.h: the statistics tail, factorize.rs:121-147)
+SKIPPED_STATS = (K.STAT_CONDEST_L, K.STAT_CONDEST_U, K.STAT_NORM_L, K.STAT_NORM_U, K.STAT_NORMEST_L_INV, K.STAT_NORMEST_U_INV,
+                 K.STAT_ONENORM, K.STAT_INFNORM, K.STAT_RESIDUAL_TEST)
+
+
+def getter_keys():
+    return sorted((name, val) for name, val in vars(K).items() if name.startswith("STAT_"))
+
+
+# Getters that count over the whole life of a handle (lu.rs:79-81): a handle with a past and a fresh one differ in them
+HISTORY_GETTERS = (K.STAT_NFACTORIZE, K.STAT_NSYMPERM_TOTAL, K.STAT_NFORREST_TOTAL, K.STAT_DEV_NUNSYMPERM_TOTAL)
+
+
+def assert_same_getters(h, o, where, skip_stats=False, history=True):
+    """Every getter of blu_amd/keys.py but those of GETTERS_NOT_COMPARED equal on the device handle h and on o, the oracle
+    or another device handle (NaN equal to NaN).  skip_stats: h has blu_hip_set_skip_stats on, so SKIPPED_STATS must read
+    0 on it instead.  history=False: o is a fresh handle, so HISTORY_GETTERS are left out."""
+    bad = []
+    for name, key in getter_keys():
+        if key in GETTERS_NOT_COMPARED or (not history and key in HISTORY_GETTERS):
+            continue
+        a = h.stat(key)
+        b = 0.0 if skip_stats and key in SKIPPED_STATS else o.stat(key)
+        if not (a == b or (np.isnan(a) and np.isnan(b))):
+            bad.append((name, a, b))
+    assert not bad, (where, bad)
+
+
+def status_of(call):
+    """The status of a BLU / OracleBLU call: what it returns (a status, or a tuple that starts with one), K.OK for a
+    result that is not a status, or the status of the error it raised (blu_amd.BluError; the oracle's RuntimeError
+    "... status <n>")."""
+    from blu_amd import BluError
+    try:
+        r = call()
+    except BluError as e:
+        return e.status
+    except RuntimeError as e:
+        return int(str(e).split()[-1])
+    if isinstance(r, tuple):
+        return r[0]
+    return r if isinstance(r, int) else K.OK
+
+
+def spoil(b_begin, b_end, b_i, b_x, kind, seed=0):
+    """A copy of a gathered B that factorize must refuse with ERROR_INVALID_ARGUMENT (singletons.rs:119-201):
+    kind "index": one row index inside a column's range set to >= m; "order": b_end[j] < b_begin[j] for one column."""
+    rng = np.random.default_rng(seed)
+    bb, be, bi, bx = b_begin.copy(), b_end.copy(), b_i.copy(), b_x.copy()
+    m = len(bb)
+    j = int(rng.choice(np.flatnonzero(be > bb)))
+    if kind == "index":
+        bi[int(rng.integers(int(bb[j]), int(be[j])))] = m + int(rng.integers(0, 5))
+    else:
+        bb[j], be[j] = be[j], bb[j]
+    return bb, be, bi, bx
