@@ -9,6 +9,7 @@ with the same method names, argument meaning and error behaviour:
     .factorize(b_begin, b_end, b_i, b_x)           BLU::factorize           blu.rs:95
     .get_factors()                                 BLU::get_factors         blu.rs:139
     .solve_dense(rhs, trans)                       BLU::solve_dense         blu.rs:182
+    solve_dense_batch(handles, rhs, trans)         solve_dense for many handles in one call (batch extension)
     .set_param / .stat                             pub fields / getters     lu.rs:11-66, 398-684
 
 There is NO CPU fallback: if the shared library is missing, or no gfx950 device is visible, this
@@ -37,6 +38,7 @@ EXPORTS = [
     "blu_hip_factorize", "blu_hip_factorize_device", "blu_hip_get_factors", "blu_hip_solve_dense",
     "blu_hip_factorize_batch", "blu_hip_version", "blu_hip_device_count", "blu_hip_last_error",
     "blu_hip_solve_sparse", "blu_hip_solve_for_update", "blu_hip_update", "blu_hip_set_skip_stats", "blu_hip_gen_lp_basis",
+    "blu_hip_solve_dense_batch",
 ]
 
 
@@ -169,6 +171,52 @@ def factorize_batch(handles, mats=None, device_ptrs=None, block=None):
         if s in (K.ERROR_DEVICE, K.ERROR_OUT_OF_MEMORY):
             raise BluError(s, h.last_error())
     return out
+
+
+def solve_dense_batch(handles, rhs=None, trans="N", device_ptrs=None):
+    """solve_dense for len(handles) handles of one device in one call (one wave per system; bit-identical per member to
+    BLU.solve_dense on the same handle and right-hand side).
+
+    rhs: list of 1-D host arrays, rhs[k] with handles[k].m entries (or an (n, m) array when every m is equal).
+        Returns (solutions, statuses): the list of solutions (float64 arrays; a member that was not solved gets zeros)
+        and the per-member statuses.
+    device_ptrs: list of (p_rhs, p_lhs) raw device pointers of m float64 each (e.g. torch tensors' data_ptr()); p_rhs ==
+        p_lhs is allowed.  Returns the statuses alone.
+    A refused call raises BluError, as does ERROR_DEVICE or ERROR_OUT_OF_MEMORY of a member; ERROR_INVALID_CALL of a
+    member without a valid factorization is only reported in its status."""
+    n = len(handles)
+    L = lib()
+    L.blu_hip_solve_dense_batch.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_char, C.c_int, C.c_void_p]
+    hs = (C.c_void_p * max(n, 1))(*[h._h for h in handles])
+    pr, pl = (C.c_void_p * max(n, 1))(), (C.c_void_p * max(n, 1))()
+    sols = None
+    if device_ptrs is not None:
+        if len(device_ptrs) != n:
+            raise ValueError("solve_dense_batch: one (p_rhs, p_lhs) pair per handle")
+        for k, (r, l) in enumerate(device_ptrs):
+            pr[k], pl[k] = int(r), int(l)
+        on_dev = 1
+    else:
+        if rhs is None or len(rhs) != n:
+            raise ValueError("solve_dense_batch: one right-hand side per handle")
+        rs = [np.ascontiguousarray(rhs[k], dtype=np.float64) for k in range(n)]
+        for k, (r, h) in enumerate(zip(rs, handles)):
+            if r.shape != (h.m,):
+                raise ValueError("solve_dense_batch: member %d: right-hand side needs m = %d entries" % (k, h.m))
+        sols = [np.zeros(h.m) for h in handles]
+        for k in range(n):
+            pr[k], pl[k] = rs[k].ctypes.data or 8, sols[k].ctypes.data or 8  # (m == 0: any non-NULL pointer)
+        on_dev = 0
+    UNTOUCHED = -12345
+    st = (C.c_int * max(n, 1))(*([UNTOUCHED] * max(n, 1)))
+    rc = L.blu_hip_solve_dense_batch(hs, n, pr, pl, trans.encode()[0:1], on_dev, st)
+    out = [int(s) for s in st][:n]
+    if rc in (K.ERROR_ARGUMENT_MISSING, K.ERROR_INVALID_ARGUMENT):  # (codes only a refusal of the whole call returns)
+        raise BluError(rc, "solve_dense_batch refused")
+    for h, s in zip(handles, out):
+        if s in (K.ERROR_DEVICE, K.ERROR_OUT_OF_MEMORY):
+            raise BluError(s, h.last_error())
+    return out if sols is None else (sols, out)
 
 
 class BLU:

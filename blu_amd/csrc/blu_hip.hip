@@ -769,7 +769,8 @@ extern "C" int blu_hip_get_factors(blu_hip *h, int64_t *rowperm, int64_t *colper
     return ok ? BLU_OK : BLU_ERROR_DEVICE;
 }
 
-// workspace of the solves that walk the factors line by line (allocated at the first use)
+// workspace of the solves that walk the factors line by line (allocated at the first use; the row-wise L pointers may
+// exist already: blu_hip_solve_dense_batch allocates those alone, ensure_lt_ws)
 static int ensure_sparse_ws(blu_hip *h)
 {
     if (h->sw_ready) return BLU_OK;
@@ -777,7 +778,7 @@ static int ensure_sparse_ws(blu_hip *h)
     SparseWs &W = h->sw;
     bool a = dalloc(h, &W.marked, M) && dalloc(h, &W.psym, M) && dalloc(h, &W.pat, M) && dalloc(h, &W.pstack, M) && dalloc(h, &W.estack, M) &&
              dalloc(h, &W.work, M) && dalloc(h, &W.xlhs, M) && dalloc(h, &W.ilhs, M) && dalloc(h, &W.xval, M) &&
-             dalloc(h, &W.out, 4) && dalloc(h, &W.lt_ptr, M + 1) && dalloc(h, &W.lt_cur, M);
+             dalloc(h, &W.out, 4) && (W.lt_ptr || dalloc(h, &W.lt_ptr, M + 1)) && (W.lt_cur || dalloc(h, &W.lt_cur, M));
     a = a && hip_ok(h, hipMemset(W.marked, 0, M * sizeof(int)), "hipMemset") &&
         hip_ok(h, hipMemset(W.work, 0, M * sizeof(double)), "hipMemset") &&
         hip_ok(h, hipMemset(W.xlhs, 0, M * sizeof(double)), "hipMemset");
@@ -904,6 +905,8 @@ extern "C" int blu_hip_solve_dense(blu_hip *h, const double *rhs, double *lhs, c
     if (!hip_ok(h, hipMemcpy(lhs, h->d_lhs, M * 8, hipMemcpyDeviceToHost), "d2h lhs")) return BLU_ERROR_DEVICE;
     return BLU_OK;
 }
+
+#include "blu_solve_batch.inc"
 
 // solve_sparse -- src/solve_sparse.rs:36-68, lu/solve_sparse.rs:11-360 (fresh factorization: nforrest == 0)
 extern "C" int blu_hip_solve_sparse(blu_hip *h, int64_t nzrhs, const uint64_t *irhs, const double *xrhs, int64_t *p_nzlhs,

@@ -1,0 +1,176 @@
+// blu_solve_batch.inc -- blu_hip_solve_dense_batch (included by blu_hip.hip): blu_hip_solve_dense for many handles in
+// one call.  Each member's system runs on one wave, the members of a kind in one launch:
+//   k_build_lt_batch         row-wise L of the fresh factorizations a forward solve needs and does not have yet
+//                            (one workgroup per member; the same array ensure_lt builds, kept for later calls)
+//   k_solve_dense_batch      fresh factorizations (nupdate == 0): the sweeps of k_solve_dense
+//   k_solve_dense_upd_batch  updated factorizations (nupdate > 0): the body of k_solve_dense_upd
+// on one stream, one synchronize at the end.  The per-member descriptors are staged on the host and uploaded once.
+
+// the row-wise L buffers alone -- what a forward dense solve reads -- for THIS factorization's L (ensure_lt allocates
+// them with the whole solve_sparse workspace; ensure_sparse_ws keeps what is allocated here)
+static int ensure_lt_ws(blu_hip *h)
+{
+    const size_t M = (size_t)h->m;
+    SparseWs &W = h->sw;
+    if (!W.lt_ptr && !dalloc(h, &W.lt_ptr, M + 1)) return BLU_ERROR_OUT_OF_MEMORY;
+    if (!W.lt_cur && !dalloc(h, &W.lt_cur, M)) return BLU_ERROR_OUT_OF_MEMORY;
+    const int64_t lnz = std::max<int64_t>((int64_t)h->hs.lused, 1);
+    if (lnz > h->sw_ltcap) {
+        dfree(W.lt_idx);
+        dfree(W.lt_val);
+        h->sw_ltcap = 0;
+        h->lt_for_nfact = -1;
+        if (!dalloc(h, &W.lt_idx, (size_t)lnz) || !dalloc(h, &W.lt_val, (size_t)lnz)) return BLU_ERROR_OUT_OF_MEMORY;
+        h->sw_ltcap = lnz;
+    }
+    return BLU_OK;
+}
+
+static size_t align_up(size_t x) { return (x + 255) & ~(size_t)255; }
+
+extern "C" int blu_hip_solve_dense_batch(blu_hip **hs, int n, const double *const *rhs, double *const *lhs, char trans,
+                                         int inputs_on_device, int *status)
+{
+    // refusals of the call as a whole: every status[k] carries the code, no handle is touched
+    auto fail_all = [&](int code) {
+        if (status)
+            for (int k = 0; k < n; k++) status[k] = code;
+        return code;
+    };
+    if (!hs || !rhs || !lhs || n < 0) return fail_all(BLU_ERROR_ARGUMENT_MISSING);
+    if (n == 0) return BLU_OK;
+    for (int k = 0; k < n; k++)
+        if (!hs[k] || !rhs[k] || !lhs[k]) return fail_all(BLU_ERROR_ARGUMENT_MISSING);
+    blu_hip *h0 = hs[0];
+    for (int k = 0; k < n; k++)
+        if (hs[k]->device != h0->device) return fail_all(BLU_ERROR_INVALID_ARGUMENT);
+    if (n > 1) { // the same handle twice = two waves on one work vector: rejected
+        std::vector<blu_hip *> sorted(hs, hs + n);
+        std::sort(sorted.begin(), sorted.end());
+        if (std::adjacent_find(sorted.begin(), sorted.end()) != sorted.end()) return fail_all(BLU_ERROR_INVALID_ARGUMENT);
+    }
+    if (hipSetDevice(h0->device) != hipSuccess) return fail_all(BLU_ERROR_DEVICE);
+    const int tr = (trans == 't' || trans == 'T') ? 1 : 0;
+
+    // per member: its kind, and what it needs before the launches
+    std::vector<int> result(n, kPending);
+    std::vector<int> fresh_build, fresh_plain, upd; // member indices
+    for (int k = 0; k < n; k++) {
+        blu_hip *h = hs[k];
+        if (h->nupdate < 0) { // solve_dense.rs:25-27
+            result[k] = BLU_ERROR_INVALID_CALL;
+            continue;
+        }
+        if (h->m == 0) {
+            result[k] = BLU_OK;
+            continue;
+        }
+        const size_t M = (size_t)h->m;
+        if (!inputs_on_device) { // staged through the handle's own buffers, as blu_hip_solve_dense does
+            if (!h->d_rhs || !h->d_lhs) {
+                dfree(h->d_rhs); dfree(h->d_lhs);
+                if (!dalloc(h, &h->d_rhs, M) || !dalloc(h, &h->d_lhs, M)) {
+                    result[k] = BLU_ERROR_OUT_OF_MEMORY;
+                    continue;
+                }
+            }
+        }
+        int st = BLU_OK;
+        std::vector<int> *kind = &fresh_plain;
+        if (h->nupdate > 0) {
+            kind = &upd;
+            st = ensure_upd(h); // (a no-op once an update was made: it needed the same)
+            if (st == BLU_OK) st = marker_room(h);
+        } else if (!tr && h->lt_for_nfact != h->nfactorize) {
+            kind = &fresh_build;
+            st = ensure_lt_ws(h);
+        }
+        if (st == BLU_OK && !inputs_on_device && !hip_ok(h, hipMemcpy(h->d_rhs, rhs[k], M * 8, hipMemcpyHostToDevice), "h2d rhs"))
+            st = BLU_ERROR_DEVICE;
+        if (st == BLU_OK) kind->push_back(k);
+        else result[k] = st;
+    }
+
+    // one staging buffer: descriptors of the fresh members (those that need the row-wise L first), then of the
+    // updated ones; read-out descriptors of the fresh ones; SolveMember of all; SparseWs of the builds, then of the
+    // updated members; UpdWs of the updated members
+    std::vector<int> order(fresh_build);
+    order.insert(order.end(), fresh_plain.begin(), fresh_plain.end());
+    const int nb = (int)fresh_build.size(), nf = (int)order.size(), nu = (int)upd.size();
+    order.insert(order.end(), upd.begin(), upd.end());
+    const int na = nf + nu;
+    bool ok = true;
+    if (na > 0) {
+        const size_t oD = 0, oO = align_up(oD + (size_t)na * sizeof(DevLU)), oM = align_up(oO + (size_t)nf * sizeof(FinishOut)),
+                     oW = align_up(oM + (size_t)na * sizeof(SolveMember)), oU = align_up(oW + (size_t)(nb + nu) * sizeof(SparseWs)),
+                     total = oU + (size_t)nu * sizeof(UpdWs);
+        std::vector<char> stage(total, 0);
+        DevLU *sD = (DevLU *)(stage.data() + oD);
+        FinishOut *sO = (FinishOut *)(stage.data() + oO);
+        SolveMember *sM = (SolveMember *)(stage.data() + oM);
+        SparseWs *sW = (SparseWs *)(stage.data() + oW);
+        UpdWs *sU = (UpdWs *)(stage.data() + oU);
+        for (int s = 0; s < na; s++) {
+            const int k = order[s];
+            blu_hip *h = hs[k];
+            sD[s] = h->D;
+            if (s < nf) sO[s] = h->O;
+            SolveMember &M = sM[s];
+            M.rhs = inputs_on_device ? rhs[k] : h->d_rhs;
+            M.lhs = inputs_on_device ? lhs[k] : h->d_lhs;
+            M.lt_ptr = h->sw.lt_ptr;
+            M.lt_idx = h->sw.lt_idx;
+            M.lt_val = h->sw.lt_val;
+            M.marker = h->marker;
+            M.pad = 0;
+            if (s < nb) sW[s] = h->sw;
+            if (s >= nf) {
+                sW[nb + (s - nf)] = h->sw;
+                sU[s - nf] = h->uw;
+            }
+        }
+        char *dbuf = nullptr;
+        if (!hip_ok(h0, hipMalloc((void **)&dbuf, total), "hipMalloc")) {
+            (void)hipGetLastError();
+            for (int s = 0; s < na; s++) result[order[s]] = BLU_ERROR_OUT_OF_MEMORY;
+        } else {
+            const DevLU *dD = (const DevLU *)(dbuf + oD);
+            const FinishOut *dO = (const FinishOut *)(dbuf + oO);
+            const SolveMember *dM = (const SolveMember *)(dbuf + oM);
+            const SparseWs *dW = (const SparseWs *)(dbuf + oW);
+            const UpdWs *dU = (const UpdWs *)(dbuf + oU);
+            hipStream_t stream = h0->stream;
+            ok = hip_ok(h0, hipMemcpyAsync(dbuf, stage.data(), total, hipMemcpyHostToDevice, stream), "h2d solve descriptors");
+            if (ok) {
+                if (nb > 0) hipLaunchKernelGGL(k_build_lt_batch, dim3(nb), dim3(1024), 0, stream, dD, dW);
+                if (nf > 0) hipLaunchKernelGGL(k_solve_dense_batch, dim3(nf), dim3(64), 0, stream, dD, dO, dM, tr);
+                if (nu > 0) hipLaunchKernelGGL(k_solve_dense_upd_batch, dim3(nu), dim3(64), 0, stream, dD + nf, dW + nb, dU, dM + nf, tr);
+                ok = hip_ok(h0, hipStreamSynchronize(stream), "k_solve_dense_batch");
+            }
+            (void)hipFree(dbuf);
+            for (int s = 0; s < na; s++) {
+                const int k = order[s];
+                blu_hip *h = hs[k];
+                if (!ok) {
+                    if (h != h0) h->err = h0->err;
+                    result[k] = BLU_ERROR_DEVICE;
+                    continue;
+                }
+                if (s < nb) h->lt_for_nfact = h->nfactorize;
+                if (s >= nf) h->marker += 4;
+                result[k] = BLU_OK;
+                if (!inputs_on_device && !hip_ok(h, hipMemcpy(lhs[k], h->d_lhs, (size_t)h->m * 8, hipMemcpyDeviceToHost), "d2h lhs"))
+                    result[k] = BLU_ERROR_DEVICE;
+            }
+        }
+    }
+    // return value: the most negative error if any member failed, else the largest status
+    int worst_err = 0, worst_pos = BLU_OK;
+    for (int k = 0; k < n; k++) {
+        const int r = result[k] == kPending ? BLU_ERROR_DEVICE : result[k];
+        if (status) status[k] = r;
+        if (r < 0) worst_err = std::min(worst_err, r);
+        else worst_pos = std::max(worst_pos, r);
+    }
+    return worst_err < 0 ? worst_err : worst_pos;
+}

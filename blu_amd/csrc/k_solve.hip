@@ -1,5 +1,5 @@
 // k_solve.hip -- solve_dense (src/lu/solve_dense.rs:7-120) for a fresh factorization (nforrest = 0),
-// one workgroup per matrix.
+// one workgroup per matrix (k_solve_dense), or one wave per member of a batch (k_solve_dense_batch).
 //
 // The reference's operation order is kept exactly, so the solution is bit-identical to it:
 //   forward     L: for k ascending   x = sum over ROW pivotrow[k] of L (row-wise copy, ascending in the
@@ -119,21 +119,15 @@ struct WRows {
     }
 };
 
-__global__ void __launch_bounds__(1024) k_solve_dense(DevLU *Ds, FinishOut *Os, const double *rhs, double *lhs, int trans, const int *lt_ptr,
-                                                      const int *lt_idx, const double *lt_val)
+// the two sweeps of one system on ONE wave: y = D.txrj holds the right-hand side (m+2 doubles of scratch: work1)
+__device__ __forceinline__ void solve_dense_sweeps(const DevG &D, const FinishOut &O, double *lhs, int trans, const int *lt_ptr,
+                                                   const int *lt_idx, const double *lt_val)
 {
-    const DevG D(Ds[blockIdx.x]);
-    const FinishOut &O = Os[blockIdx.x];
-    const int tid = threadIdx.x, nt = blockDim.x, lane = lane_id();
+    const int lane = lane_id();
     const int m = D.m;
     const int rank = D.s->rank;
-    gdouble_p y = D.txrj;      // m+2 doubles of scratch: work1
+    gdouble_p y = D.txrj;
     gdouble_p x_out = (gdouble_p)lhs;
-
-    for (int k = tid; k < m; k += nt) y[k] = rhs[k]; // solve_dense.rs:34 / :77
-    __syncthreads();
-    if (wave_id() != 0) return;
-
     const auto at_aux = [](int, const ColPtr &P) { return P.aux; };
     const auto at_aux2 = [](int, const ColPtr &P) { return P.aux2; };
     const auto sub_dot = [](int, const ColPtr &P, double dot, double own, bool &store) {
@@ -159,4 +153,44 @@ __global__ void __launch_bounds__(1024) k_solve_dense(DevLU *Ds, FinishOut *Os, 
         const LStage CS{D.lbeg, D.lidx, D.prow, nullptr, D.lval, m};
         sweep_dot(CS, m - 1, -1, m, x_out, at_aux, sub_dot);
     }
+}
+
+__global__ void __launch_bounds__(1024) k_solve_dense(DevLU *Ds, FinishOut *Os, const double *rhs, double *lhs, int trans, const int *lt_ptr,
+                                                      const int *lt_idx, const double *lt_val)
+{
+    const DevG D(Ds[blockIdx.x]);
+    const int tid = threadIdx.x, nt = blockDim.x;
+    const int m = D.m;
+    gdouble_p y = D.txrj; // m+2 doubles of scratch: work1
+    for (int k = tid; k < m; k += nt) y[k] = rhs[k]; // solve_dense.rs:34 / :77
+    __syncthreads();
+    if (wave_id() != 0) return;
+    solve_dense_sweeps(D, Os[blockIdx.x], lhs, trans, lt_ptr, lt_idx, lt_val);
+}
+
+// ------------------------------------------------------------------------------------------------
+// blu_hip_solve_dense_batch: one system per member, each on a workgroup of ONE wave (the sweeps above leave the
+// other waves of k_solve_dense idle after the copy), every member of the launch resident at once up to the
+// occupancy.  Ds / Os / Ms: the members' descriptors, gathered into arrays once per call; rhs == lhs allowed.
+// ------------------------------------------------------------------------------------------------
+struct SolveMember {
+    const double *rhs;
+    double *lhs;
+    const int *lt_ptr, *lt_idx; // row-wise L of the member ('N' solves; null otherwise)
+    const double *lt_val;
+    int marker; // lu.marker at the launch (updated factorizations, k_solve_dense_upd_batch)
+    int pad;
+};
+
+__global__ void __launch_bounds__(64) k_solve_dense_batch(const DevLU *__restrict__ Ds, const FinishOut *__restrict__ Os,
+                                                          const SolveMember *__restrict__ Ms, int trans)
+{
+    const int b = blockIdx.x;
+    const DevG D(Ds[b]);
+    const SolveMember M = Ms[b];
+    const int m = D.m;
+    gdouble_p y = D.txrj;
+    for (int k = lane_id(); k < m; k += 64) y[k] = M.rhs[k]; // solve_dense.rs:34 / :77
+    wave_mem_sync();
+    solve_dense_sweeps(D, Os[b], M.lhs, trans, M.lt_ptr, M.lt_idx, M.lt_val);
 }

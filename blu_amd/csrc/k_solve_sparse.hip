@@ -507,24 +507,21 @@ __global__ void __launch_bounds__(64) k_solve_sparse(DevLU *Ds, FinishOut *Os, S
 
 // Row-wise L in the reference's order (build_factors.rs:243-274): row i holds, for every column it has
 // an entry in, the row index of that column's pivot, ascending in the columns' pivot order.
-// One workgroup: count, scan, scatter (unordered), then sort each short row by pivot position.
-__global__ void __launch_bounds__(1024) k_build_lt(DevLU *Ds, SparseWs W)
+// One workgroup: count, scan, scatter (unordered), then sort each short row by pivot position.  part: nt ints of LDS.
+__device__ __forceinline__ void build_lt_body(const DevG &D, int *lt_ptr, int *lt_idx, double *lt_val, int *lt_cur, int *carry, int *part)
 {
-    const DevG D(Ds[0]);
     const int tid = threadIdx.x, nt = blockDim.x;
     const int m = D.m;
-    __shared__ int carry;
-    __shared__ int part[1024];
-    for (int i = tid; i < m; i += nt) W.lt_cur[i] = 0;
-    if (tid == 0) carry = 0;
+    for (int i = tid; i < m; i += nt) lt_cur[i] = 0;
+    if (tid == 0) *carry = 0;
     __syncthreads();
     const int lend = D.lbeg[m];
-    for (int p = tid; p < lend; p += nt) atomicAdd(&W.lt_cur[D.lidx[p]], 1);
+    for (int p = tid; p < lend; p += nt) atomicAdd(&lt_cur[D.lidx[p]], 1);
     __syncthreads();
     // exclusive scan of the row counts, 1024 at a time
     for (int base = 0; base < m; base += nt) {
         const int i = base + tid;
-        const int c = i < m ? W.lt_cur[i] : 0;
+        const int c = i < m ? lt_cur[i] : 0;
         part[tid] = c;
         __syncthreads();
         for (int o = 1; o < nt; o <<= 1) {
@@ -533,41 +530,56 @@ __global__ void __launch_bounds__(1024) k_build_lt(DevLU *Ds, SparseWs W)
             part[tid] += v;
             __syncthreads();
         }
-        const int excl = carry + part[tid] - c;
+        const int excl = *carry + part[tid] - c;
         if (i < m) {
-            W.lt_ptr[i] = excl;
-            W.lt_cur[i] = excl;
+            lt_ptr[i] = excl;
+            lt_cur[i] = excl;
         }
         __syncthreads();
-        if (tid == nt - 1) carry += part[tid];
+        if (tid == nt - 1) *carry += part[tid];
         __syncthreads();
     }
-    if (tid == 0) W.lt_ptr[m] = carry;
+    if (tid == 0) lt_ptr[m] = *carry;
     __syncthreads();
     // scatter: entry (row i, stage k) -> row i, keyed by k for now
     for (int k = tid; k < m; k += nt) {
         for (int p = D.lbeg[k]; p < D.lbeg[k + 1]; p++) {
-            const int q = atomicAdd(&W.lt_cur[D.lidx[p]], 1);
-            W.lt_idx[q] = k;
-            W.lt_val[q] = D.lval[p];
+            const int q = atomicAdd(&lt_cur[D.lidx[p]], 1);
+            lt_idx[q] = k;
+            lt_val[q] = D.lval[p];
         }
     }
     __syncthreads();
     // sort every row by k (rows are short), then replace k by the pivot row of stage k
     for (int i = tid; i < m; i += nt) {
-        const int b = W.lt_ptr[i], e = W.lt_ptr[i + 1];
+        const int b = lt_ptr[i], e = lt_ptr[i + 1];
         for (int p = b + 1; p < e; p++) {
-            const int k = W.lt_idx[p];
-            const double v = W.lt_val[p];
+            const int k = lt_idx[p];
+            const double v = lt_val[p];
             int q = p - 1;
-            while (q >= b && W.lt_idx[q] > k) {
-                W.lt_idx[q + 1] = W.lt_idx[q];
-                W.lt_val[q + 1] = W.lt_val[q];
+            while (q >= b && lt_idx[q] > k) {
+                lt_idx[q + 1] = lt_idx[q];
+                lt_val[q + 1] = lt_val[q];
                 q--;
             }
-            W.lt_idx[q + 1] = k;
-            W.lt_val[q + 1] = v;
+            lt_idx[q + 1] = k;
+            lt_val[q + 1] = v;
         }
-        for (int p = b; p < e; p++) W.lt_idx[p] = D.prow[W.lt_idx[p]];
+        for (int p = b; p < e; p++) lt_idx[p] = D.prow[lt_idx[p]];
     }
+}
+__global__ void __launch_bounds__(1024) k_build_lt(DevLU *Ds, SparseWs W)
+{
+    __shared__ int carry;
+    __shared__ int part[1024];
+    build_lt_body(DevG(Ds[0]), W.lt_ptr, W.lt_idx, W.lt_val, W.lt_cur, &carry, part);
+}
+// the same for a batch of solves (blu_hip_solve_dense_batch): one workgroup per member, Ds[b] with the row-wise L
+// buffers of Ws[b]
+__global__ void __launch_bounds__(1024) k_build_lt_batch(const DevLU *Ds, const SparseWs *Ws)
+{
+    __shared__ int carry;
+    __shared__ int part[1024];
+    const SparseWs &W = Ws[blockIdx.x];
+    build_lt_body(DevG(Ds[blockIdx.x]), W.lt_ptr, W.lt_idx, W.lt_val, W.lt_cur, &carry, part);
 }

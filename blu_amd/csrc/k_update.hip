@@ -983,9 +983,9 @@ __device__ __forceinline__ double wave_ordered_dot(const double *vec, const int 
     return x;
 }
 
-__global__ void __launch_bounds__(64) k_solve_dense_upd(DevLU *Ds, SparseWs W, UpdWs U, const double *rhs, double *lhs, int trans, int marker)
+__device__ __forceinline__ void solve_dense_upd_wave(const DevG &D, const SparseWs &W, const UpdWs &U, const double *rhs, double *lhs, int trans,
+                                                     int marker)
 {
-    const DevG D(Ds[0]);
     const int lane = lane_id();
     const int m = D.m;
     UpdState *st = U.st;
@@ -1049,4 +1049,18 @@ __global__ void __launch_bounds__(64) k_solve_dense_upd(DevLU *Ds, SparseWs W, U
             wave_mem_sync();
         }
     }
+}
+
+__global__ void __launch_bounds__(64) k_solve_dense_upd(DevLU *Ds, SparseWs W, UpdWs U, const double *rhs, double *lhs, int trans, int marker)
+{
+    solve_dense_upd_wave(DevG(Ds[0]), W, U, rhs, lhs, trans, marker);
+}
+// the same for the members of blu_hip_solve_dense_batch with an updated factorization: one wave per member, the
+// workspaces of member b in Ws[b] / Us[b], its right-hand side, solution and marker in Ms[b]
+__global__ void __launch_bounds__(64) k_solve_dense_upd_batch(const DevLU *__restrict__ Ds, const SparseWs *__restrict__ Ws,
+                                                              const UpdWs *__restrict__ Us, const SolveMember *__restrict__ Ms, int trans)
+{
+    const int b = blockIdx.x;
+    const SolveMember M = Ms[b];
+    solve_dense_upd_wave(DevG(Ds[b]), Ws[b], Us[b], M.rhs, M.lhs, trans, M.marker);
 }

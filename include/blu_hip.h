@@ -203,6 +203,25 @@ int blu_hip_factorize_batch(blu_hip **h, int n,
                             const uint64_t *const *b_i, const double *const *b_x,
                             const uint64_t *b_i_len, int inputs_on_device, int *status);
 
+/* Batch extension: blu_hip_solve_dense for n handles on one device in one call, bit-identical per member to
+ * blu_hip_solve_dense on the same handle and right-hand side.  rhs[k] / lhs[k] hold m_k doubles of member k (members
+ * may differ in m); with inputs_on_device != 0 they are device pointers on the handles' device, else host arrays.
+ * rhs[k] == lhs[k] is allowed; the arrays of two different members must not overlap.  trans applies to every member
+ * ('t' / 'T' transposed, anything else forward).  Each system runs on ONE wave (k_solve_dense_batch for a fresh
+ * factorization, k_solve_dense_upd_batch after updates): one launch per kind and one synchronize for the call, no copy
+ * per member with device inputs (host inputs are staged through each handle's own solve buffers).
+ * status[k]: BLU_OK (also for m == 0), BLU_ERROR_INVALID_CALL for a handle without a valid factorization,
+ * BLU_ERROR_OUT_OF_MEMORY if its workspace could not be allocated, BLU_ERROR_DEVICE; the other members are solved
+ * regardless.  Refused as a whole, every status[k] carrying the refusal and no handle changed: NULL arrays, handles or
+ * per-member pointers, n < 0 (BLU_ERROR_ARGUMENT_MISSING), the same handle twice or handles on different devices
+ * (BLU_ERROR_INVALID_ARGUMENT).  n == 0 returns BLU_OK.  Returns the most negative member status, else the largest.
+ * Device memory: a forward solve of a fresh factorization builds its row-wise L (k_build_lt_batch) as
+ * blu_hip_solve_dense does, 8 bytes per row plus 12 bytes per L entry per handle, kept for later solves of the same
+ * factorization; host inputs add the handle's 16 bytes per row of solve buffers; for its duration the call borrows
+ * under 1 KB per member for the gathered descriptors. */
+int blu_hip_solve_dense_batch(blu_hip **h, int n, const double *const *rhs, double *const *lhs, char trans,
+                              int inputs_on_device, int *status);
+
 /* factorize() ends with the statistics tail of src/factorize.rs:121-147 (condest(L), condest(U),
  * residual_test; getters BLU_STAT_CONDEST_* .. BLU_STAT_RESIDUAL_TEST).  It is a chain of 8 triangular
  * sweeps (~17 % of the factorize time at 100k); a caller that never reads those getters can switch
