@@ -125,14 +125,12 @@ def factorize_batch(handles, mats=None, device_ptrs=None, block=None):
     (b_begin, b_end, b_i, b_x): column j is b_i[b_begin[j]..b_end[j]), b_x[...] (columns gathered from a larger
     matrix, in any order and with gaps between them), or
     device_ptrs: list of (p_begin, p_end, p_i, p_x, nnz_len) raw device pointers (inputs already in HBM).
+    block: accepted for the callers that pass it and ignored (the pivot kernels of a batch have fixed workgroup sizes).
     Returns the list of per-handle statuses (reference Status numbering)."""
     n = len(handles)
     L = lib()
     L.blu_hip_factorize_batch.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
                                           C.c_void_p, C.c_int, C.c_void_p]
-    L.blu_hip_dbg_set_batch_block.argtypes = [C.c_void_p, C.c_int]
-    if block:
-        L.blu_hip_dbg_set_batch_block(handles[0]._h, int(block))
     hs = (C.c_void_p * n)(*[h._h for h in handles])
     pb, pe, pi, px = (C.c_void_p * n)(), (C.c_void_p * n)(), (C.c_void_p * n)(), (C.c_void_p * n)()
     ln = (C.c_uint64 * n)()
@@ -397,7 +395,7 @@ class BLU:
 
     def dbg_set_pivot_kernel(self, which):
         """0 = default (one basis: k_pivot_loop; batch: k_pivot_loop_wave2 while every workgroup is resident, else
-        k_pivot_loop_wave), 1 = one wave per matrix, 2 = multi-wave workgroups, 3 = two waves per matrix"""
+        k_pivot_loop_wave), 1 = one wave per matrix, 3 = two waves per matrix; any other value raises INVALID_ARGUMENT"""
         lib().blu_hip_dbg_set_pivot_kernel.argtypes = [C.c_void_p, C.c_int]
         st = lib().blu_hip_dbg_set_pivot_kernel(self._h, int(which))
         if st != K.OK:

@@ -154,19 +154,18 @@ static bool batch_init(BatchCtx &B, blu_hip **hs, int n)
     B.st.assign(n, -1);
     B.result.assign(n, kPending);
     blu_hip *h0 = hs[0];
+    B.block_pivot = h0->block_threads;
     if (n == 1) {
         B.dD = h0->dD;
         B.dO = h0->dO;
         B.stream = h0->stream;
         for (int k = 0; k < 4; k++) B.ev[k] = h0->ev[k];
-        B.block_pivot = h0->block_threads;
     } else {
         B.owns_arrays = true;
         if (!dalloc(h0, &B.dD, n) || !dalloc(h0, &B.dO, n)) return false;
         if (!hip_ok(h0, hipStreamCreate(&B.stream), "hipStreamCreate")) return false;
         for (int k = 0; k < 4; k++)
             if (!hip_ok(h0, hipEventCreate(&B.ev[k]), "hipEventCreate")) return false;
-        B.block_pivot = h0->batch_block;
         B.block_other = h0->batch_block_other;
         B.block_stats = h0->batch_block_stats;
     }
@@ -259,13 +258,13 @@ static int batch_grid(const blu_hip *h0, int n)
     return n < g ? n : g;
 }
 
-// dense work columns pivot_any needs in D.gwork: one per wave of the pivot kernel batch_pivot_and_finish will launch (the
-// wave kernels: 1 or 2), and never fewer than the 9 columns of the statistics
+// dense work columns pivot_any needs in D.gwork: one per wave of the pivot kernel batch_pivot_and_finish will launch
+// (k_pivot_loop: one per wave of its workgroup; the wave kernels: 1 or 2), and never fewer than the 9 columns of the
+// statistics
 static int pivot_work_columns(const BatchCtx &B)
 {
-    const blu_hip *h0 = B.hs[0];
-    const bool wave_kernel = h0->pivot_kernel == 1 || h0->pivot_kernel == 3 || (h0->pivot_kernel == 0 && B.n > 1);
-    return std::max(9, wave_kernel ? 2 : B.block_pivot / 64);
+    const bool workgroup_kernel = B.hs[0]->pivot_kernel == 0 && B.n == 1; // k_pivot_loop
+    return std::max(9, workgroup_kernel ? B.block_pivot / 64 : 2);
 }
 
 static bool batch_pivot_and_finish(BatchCtx &B)
@@ -286,7 +285,7 @@ static bool batch_pivot_and_finish(BatchCtx &B)
             } else {
                 hipLaunchKernelGGL(k_pivot_loop_wave2, dim3(n), dim3(128), 0, B.stream, B.dD, (int)h0->stop_at);
             }
-        } else if (h0->pivot_kernel == 1 || (h0->pivot_kernel == 0 && n > 1)) {
+        } else if (h0->pivot_kernel == 1 || n > 1) {
             which = 1;
             if (n <= h0->wave_r3_max) {
                 regs = 3;
@@ -294,11 +293,8 @@ static bool batch_pivot_and_finish(BatchCtx &B)
             } else {
                 hipLaunchKernelGGL(k_pivot_loop_wave, dim3(n), dim3(64), 0, B.stream, B.dD, (int)h0->stop_at);
             }
-        } else if (n > 1 && B.block_pivot <= 256) {
-            which = 2;
-            hipLaunchKernelGGL(k_pivot_loop_batch, dim3(n), dim3(B.block_pivot), 0, B.stream, B.dD, (int)h0->stop_at);
         } else {
-            which = 0;
+            which = 0; // (one basis)
             hipLaunchKernelGGL(k_pivot_loop, dim3(n), dim3(B.block_pivot), 0, B.stream, B.dD, (int)h0->stop_at);
         }
         for (int k = 0; k < n; k++) B.hs[k]->last_pivot_kernel = which, B.hs[k]->last_pivot_regs = regs;

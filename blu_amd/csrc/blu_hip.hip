@@ -18,33 +18,21 @@
 #include "blu_dev.h"
 #include "k_finish.hip"
 #define BLU_NS pv_single
-#define BLU_CFG_BATCH 0
 #define BLU_CFG_WAVE 0
 #include "k_pivot.hip"
 #undef BLU_NS
-#undef BLU_CFG_BATCH
-#define BLU_NS pv_batch
-#define BLU_CFG_BATCH 1
-#include "k_pivot.hip"
-#undef BLU_NS
-#undef BLU_CFG_BATCH
 #undef BLU_CFG_WAVE
 #define BLU_NS pv_wave
-#define BLU_CFG_BATCH 1
 #define BLU_CFG_WAVE 1
 #include "k_pivot.hip"
 #undef BLU_NS
-#undef BLU_CFG_BATCH
 #undef BLU_CFG_WAVE
 #define BLU_NS pv_wave2
-#define BLU_CFG_BATCH 1
 #define BLU_CFG_WAVE 2
 #include "k_pivot.hip"
 #undef BLU_NS
-#undef BLU_CFG_BATCH
 #undef BLU_CFG_WAVE
 using pv_single::k_pivot_loop;
-using pv_batch::k_pivot_loop_batch;
 using pv_wave::k_pivot_loop_wave;
 using pv_wave::k_pivot_loop_wave_r3;
 using pv_wave2::k_pivot_loop_wave2;
@@ -76,10 +64,9 @@ struct blu_hip {
     FinishOut O;       // device output buffers of get_factors
     FinishOut *dO;
     FinishOut *oslot;
-    int batch_block;   // workgroup size of the pivot kernel when this handle leads a batch
     int batch_block_other, batch_block_stats; // workgroup sizes of k_prep / k_setup / k_finish and of k_stats in a batch
     int no_out_alias;  // diagnostic: 1 = canonical factors always in buffers of their own (see ensure_out)
-    int pivot_kernel;  // 0 = default (one basis: k_pivot_loop; batch: k_pivot_loop_wave2 while all its workgroups are resident, else k_pivot_loop_wave), 1 = k_pivot_loop_wave, 2 = the multi-wave kernels, 3 = k_pivot_loop_wave2
+    int pivot_kernel;  // 0 = default (one basis: k_pivot_loop; batch: k_pivot_loop_wave2 while all its workgroups are resident, else k_pivot_loop_wave), 1 = k_pivot_loop_wave, 3 = k_pivot_loop_wave2
     int64_t out_lcap, out_ucap;
     bool out_in_arena; // the canonical L / U of the last factorize live inside the (then dead) column arena, not in buffers of their own
     // owned device copies of the caller's B (blu_hip_factorize with host arrays)
@@ -333,7 +320,6 @@ extern "C" blu_hip *blu_hip_new(int64_t m, int64_t b_nz, int device)
     h->d_rhs = h->d_lhs = nullptr;
     h->dslot = h->dD;
     h->oslot = h->dO;
-    h->batch_block = 256;
     {   // diagnostic: which pivot kernel this handle launches (read once; blu_hip_dbg_set_pivot_kernel overrides)
         const char *bo = getenv("BLU_BATCH_OTHER"), *bs = getenv("BLU_BATCH_STATS");
         h->batch_block_other = bo ? atoi(bo) : 512; // (512 = two waves per SIMD with the registers of the register sorts: 8-15 % faster than 256, round 4)
@@ -343,7 +329,7 @@ extern "C" blu_hip *blu_hip_new(int64_t m, int64_t b_nz, int device)
         h->no_out_alias = getenv("BLU_NO_OUT_ALIAS") ? 1 : 0;
         const char *pk = getenv("BLU_PIVOT_KERNEL");
         h->pivot_kernel = pk ? atoi(pk) : 0;
-        if (h->pivot_kernel < 0 || h->pivot_kernel > 3) h->pivot_kernel = 0;
+        if (h->pivot_kernel != 1 && h->pivot_kernel != 3) h->pivot_kernel = 0;
     }
     if (ok) { // chip-wide phases: as many workgroups as are certainly co-resident, at most 64 (one per CU of two XCDs' worth)
         int nb = 0, best = 1 << 30;
@@ -484,8 +470,8 @@ extern "C" double blu_hip_get_stat(const blu_hip *h, int key)
     case BLU_STAT_TIME_FACTORIZE: return h->t_total;
     // lu.time_singletons / time_search_pivot / time_elim_pivot (lu.rs:560-572): device seconds of the last factorize.  The
     // singleton phase is k_prep.  Search and elimination run inside ONE persistent kernel; its device time is split by
-    // the shader-clock phase counters of the diagnostic build (`make prof`: prof[0] = search + set-up of the multi-wave
-    // kernel) when they were collected, otherwise the whole kernel time is reported as elimination and the search as 0.
+    // the shader-clock phase counters of the diagnostic build (`make prof`: prof[0] = search + set-up of k_pivot_loop)
+    // when they were collected, otherwise the whole kernel time is reported as elimination and the search as 0.
     case BLU_STAT_TIME_SINGLETONS: return h->t_phase[0];
     case BLU_STAT_TIME_SEARCH_PIVOT: {
         double tot = 0.0;
@@ -533,7 +519,7 @@ extern "C" double blu_hip_get_stat(const blu_hip *h, int key)
     case 114: return (double)h->D.carena_cap;
     case 115: return (double)h->D.lcap;
     case 120: return (double)h->last_pivot_regs; // waves per SIMD its register budget was set for (the _r3 variants of the wave kernels: 3; else 4)
-    case 118: return (double)h->last_pivot_kernel; // which pivot kernel the last factorize of this handle ran: 0 k_pivot_loop, 1 k_pivot_loop_wave, 2 k_pivot_loop_batch, 3 k_pivot_loop_wave2
+    case 118: return (double)h->last_pivot_kernel; // which pivot kernel the last factorize of this handle ran: 0 k_pivot_loop, 1 k_pivot_loop_wave, 3 k_pivot_loop_wave2 (2 is not used)
     case 119: return (double)s.fill_paths; // bit 0 / bit 1: k_prep / k_finish filled through buckets (k_bucket.h)
     case 57: return (double)s.err_line;
     case 58: return (double)s.status;
@@ -1011,12 +997,6 @@ extern "C" int blu_hip_set_skip_stats(blu_hip *h, int on)
     h->skip_stats = on ? 1 : 0;
     return BLU_OK;
 }
-extern "C" int blu_hip_dbg_set_batch_block(blu_hip *h, int threads)
-{
-    if (!h || threads < 64 || threads > 1024 || (threads & 63)) return BLU_ERROR_INVALID_ARGUMENT;
-    h->batch_block = threads;
-    return BLU_OK;
-}
 // workgroups of the chip-wide O(nnz) phases of a single factorize (1: one workgroup, as inside a batch)
 extern "C" int blu_hip_dbg_set_grid_blocks(blu_hip *h, int nblocks)
 {
@@ -1024,11 +1004,10 @@ extern "C" int blu_hip_dbg_set_grid_blocks(blu_hip *h, int nblocks)
     h->grid_blocks = nblocks;
     return BLU_OK;
 }
-// 0 = default, 1 = one wave per matrix (k_pivot_loop_wave), 2 = multi-wave workgroups (k_pivot_loop / k_pivot_loop_batch),
-// 3 = two waves per matrix (k_pivot_loop_wave2)
+// 0 = default, 1 = one wave per matrix (k_pivot_loop_wave), 3 = two waves per matrix (k_pivot_loop_wave2)
 extern "C" int blu_hip_dbg_set_pivot_kernel(blu_hip *h, int which)
 {
-    if (!h || which < 0 || which > 3) return BLU_ERROR_INVALID_ARGUMENT;
+    if (!h || (which != 0 && which != 1 && which != 3)) return BLU_ERROR_INVALID_ARGUMENT;
     h->pivot_kernel = which;
     return BLU_OK;
 }

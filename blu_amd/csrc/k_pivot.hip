@@ -18,11 +18,11 @@
 //   * arithmetic: a = xrj / pivot; w -= a * c with separate roundings (no FMA)
 #include "blu_dev.h"
 
-// This file is compiled TWICE into one translation unit (blu_hip.hip), each time inside its own namespace:
-//   pv_single   k_pivot_loop        one matrix, one 1024-thread workgroup, the full-size LDS working set
-//   pv_batch    k_pivot_loop_batch  many matrices, small workgroups, BLU_CFG_BATCH: a working set sized for the
-//                                    shapes that make up practically all pivots, so that many workgroups share a CU
-// (shapes beyond the small working set take the general paths, as in the other configuration).
+// This file is compiled three times into one translation unit (blu_hip.hip), each time inside its own namespace:
+//   pv_single   k_pivot_loop                         one matrix, one 1024-thread workgroup, the LDS working set of
+//                                                     k_pivot_fast.hip
+//   pv_wave     k_pivot_loop_wave, _wave_r3          a batch of matrices, one wave each (BLU_CFG_WAVE 1, k_pivot_wave.hip)
+//   pv_wave2    k_pivot_loop_wave2, _wave2_r3        a batch of matrices, two waves each (BLU_CFG_WAVE 2)
 namespace BLU_NS {
 
 // A failed check also raises this LDS flag, so the pivot loop can stop at the next pivot boundary
@@ -41,7 +41,7 @@ __shared__ int g_pivot_err_line; // source line of a bounded loop that overran (
 #if BLU_CFG_WAVE
 #include "k_pivot_wave_types.h" // one wave per matrix (k_pivot_wave.hip)
 #else
-#include "k_pivot_fast_types.h" // (re-included per configuration: no include guard)
+#include "k_pivot_fast_types.h" // one 1024-thread workgroup per matrix (k_pivot_fast.hip)
 #endif
 
 // Diagnostic build (-DBLU_PROFILE, `make prof`): thread 0 stamps the shader clock at phase boundaries
@@ -107,7 +107,7 @@ struct alignas(16) Sm {
 #if BLU_CFG_WAVE
     double swork[WV_WCAP]; // the dense work column of the one wave (general paths: 64 entries) = the matrix of old values of k_pivot_wave.hip; all zero between pivots
 #else
-    double swork[16 * 64]; // one dense work column per wave; LAST member: the batch kernel allocates 4 of the 16
+    double swork[16 * 64]; // one dense work column per wave
 #endif
 };
 
@@ -1218,10 +1218,7 @@ __device__ COLD void setup_pivot_general(const DevGP &D, Sm *sm)
 #if BLU_CFG_WAVE
 #include "k_pivot_wave.hip" // its own pivot loop and kernel
 #else
-// BATCH: the 4-wave workgroups of the batch kernel cannot spare a wave for the split list update and the
-// early search; leaving that code out also relieves its tighter register budget.
-// mc: the metadata cache of the single-matrix kernel (k_pivot_fast_types.h), nullptr in the batch kernel
-template <bool BATCH>
+// mc: the LDS copies of the list heads and what the next search reuses of the previous pivot (k_pivot_fast_types.h)
 __device__ __forceinline__ void pivot_loop_body(DevLU *Ds, int stop_at, Sm *sm, Mc *mc)
 {
     const DevGP D(&Ds[blockIdx.x]);
@@ -1264,7 +1261,7 @@ __device__ __forceinline__ void pivot_loop_body(DevLU *Ds, int stop_at, Sm *sm, 
         g_pivot_err = 0;
         g_pivot_err_line = 0;
     }
-    if (mc) mc_reset(D, mc, tid, (int)blockDim.x);
+    mc_reset(D, mc, tid, (int)blockDim.x);
     __syncthreads();
 
     // Three workgroup barriers per pivot: wave 0 alone runs [record previous pivot -> loop head -> search
@@ -1285,7 +1282,7 @@ __device__ __forceinline__ void pivot_loop_body(DevLU *Ds, int stop_at, Sm *sm, 
             wave_mem_sync();
             // something wrote list links straight to global memory since the last search (a general pivot path,
             // remove_col, the empty-column step): reload the LDS copies of the list heads
-            const bool heads_stale = mc && mc->dirty;
+            const bool heads_stale = mc->dirty;
             WAVE_LOCKSTEP(); // (every lane has read the flag before lane 0 clears it)
             if (heads_stale) {
                 mc_reset(D, mc, lane, 64);
@@ -1298,7 +1295,7 @@ __device__ __forceinline__ void pivot_loop_body(DevLU *Ds, int stop_at, Sm *sm, 
             if (!sm->head_exit) {
                 bool handled = false;
                 if (sm->need_search) {
-                    if (D.search_rows == 0 && !D.no_fast) handled = markowitz_fast<BATCH>(D, sm, mc, ew_mcb, ew_fb);
+                    if (D.search_rows == 0 && !D.no_fast) handled = markowitz_fast(D, sm, mc, ew_mcb, ew_fb);
                     if (!handled) {
                         if (D.search_rows == 0) markowitz_wave(D, sm);
                         else if (lane == 0) markowitz_serial(D, sm);
@@ -1326,7 +1323,7 @@ __device__ __forceinline__ void pivot_loop_body(DevLU *Ds, int stop_at, Sm *sm, 
             __syncthreads(); // every thread has read sm->pr / sm->pc before thread 0 rewrites them
             if (tid == 0) {
                 list_remove1(D.cflink, D.cblink, pc);
-                if (mc) mc->dirty = 1;
+                mc->dirty = 1;
                 sm->pc = -1;
                 sm->rankdef++;
                 sm->kinds[5]++;
@@ -1341,10 +1338,10 @@ __device__ __forceinline__ void pivot_loop_body(DevLU *Ds, int stop_at, Sm *sm, 
         const int nz_col = dB.x, nz_row = dB.y;
         const int kind = dC.x;
         bool ok = true;
-        if (kind == 1) fast_small<BATCH>(D, sm, mc, pr, pc, nz_col, nz_row, ew_mcb, ew_fb);
-        else if (kind == 2) fast_scol<BATCH>(D, sm, mc, pr, pc, nz_row, dC.y, ew_mcb, ew_fb);
+        if (kind == 1) fast_small(D, sm, mc, pr, pc, nz_col, nz_row, ew_mcb, ew_fb);
+        else if (kind == 2) fast_scol(D, sm, mc, pr, pc, nz_row, dC.y, ew_mcb, ew_fb);
         else {
-            if (mc && tid == 0) mc->dirty = 1; // the general paths work on global memory only
+            if (tid == 0) mc->dirty = 1; // the general paths work on global memory only
             if (nz_row == 1) ok = pivot_singleton_row(D, sm);
             else if (nz_col == 1) ok = pivot_singleton_col(D, sm);
             else if (nz_col == 2) ok = pivot_doubleton_col(D, sm);
@@ -1427,7 +1424,7 @@ __device__ __forceinline__ void pivot_loop_body(DevLU *Ds, int stop_at, Sm *sm, 
                     const int j = D.uidx[pos];
                     if (D.colmax[j] == 0.0 || D.colmax[j] < D.abstol) {
                         remove_col_serial(D, sm, j);
-                        if (mc) mc->dirty = 1;
+                        mc->dirty = 1;
                     }
                 }
             }
@@ -1468,33 +1465,14 @@ __device__ __forceinline__ void pivot_loop_body(DevLU *Ds, int stop_at, Sm *sm, 
     }
 }
 
-#endif // !BLU_CFG_WAVE
-#if BLU_CFG_WAVE
-#elif !BLU_CFG_BATCH
 // One matrix: all 16 waves of a CU, 128 VGPRs.
 __global__ void __launch_bounds__(1024) k_pivot_loop(DevLU *Ds, int stop_at)
 {
     __shared__ Sm smem;
     __shared__ Mc mcache;
-    pivot_loop_body<false>(Ds, stop_at, &smem, &mcache);
+    pivot_loop_body(Ds, stop_at, &smem, &mcache);
 }
-#else
-// Many matrices (batch): workgroups of <= BLU_BATCH_THREADS threads, so only that many of the 16 per-wave work
-// columns at the end of Sm are allocated, and a register budget for BLU_BATCH_WAVES waves per SIMD.  LDS is handed
-// out in 1280-byte granules.
-#ifndef BLU_BATCH_WAVES
-#define BLU_BATCH_WAVES 6
-#endif
-#ifndef BLU_BATCH_THREADS
-#define BLU_BATCH_THREADS 256
-#endif
-__global__ void __launch_bounds__(BLU_BATCH_THREADS) BLU_WAVES_PER_EU(BLU_BATCH_WAVES, BLU_BATCH_WAVES)
-k_pivot_loop_batch(DevLU *Ds, int stop_at)
-{
-    __shared__ __attribute__((aligned(16))) char raw[sizeof(Sm) - (16 - BLU_BATCH_THREADS / 64) * 64 * sizeof(double)];
-    pivot_loop_body<true>(Ds, stop_at, reinterpret_cast<Sm *>(raw), nullptr);
-}
-#endif
+#endif // !BLU_CFG_WAVE
 
 } // namespace BLU_NS
 #undef PROF_STAMP

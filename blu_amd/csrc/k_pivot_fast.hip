@@ -125,7 +125,6 @@ __device__ __forceinline__ void hash_find3(const unsigned long long *H, int k1, 
 }
 // ------------------------------------------------------------------------------------------------
 // Links of the column count lists with the heads / tails of the short lists in LDS (Mc, k_pivot_fast_types.h).
-// mc == nullptr (batch kernel): plain global accesses; every branch on mc folds away after inlining.
 // ------------------------------------------------------------------------------------------------
 struct LinksC {
     const DevGP &D;
@@ -133,26 +132,26 @@ struct LinksC {
     __device__ __forceinline__ int fl(int e) const
     {
         const int k = e - D.m;
-        if (mc && k >= 0 && k < MC_HEADS) return mc->hf[k];
+        if (k >= 0 && k < MC_HEADS) return mc->hf[k];
         return D.cflink[e];
     }
     __device__ __forceinline__ int bl(int e) const
     {
         const int k = e - D.m;
-        if (mc && k >= 0 && k < MC_HEADS) return mc->hb[k];
+        if (k >= 0 && k < MC_HEADS) return mc->hb[k];
         return D.cblink[e];
     }
     __device__ __forceinline__ void set_fl(int e, int v) const
     {
         D.cflink[e] = v;
         const int k = e - D.m;
-        if (mc && k >= 0 && k < MC_HEADS) mc->hf[k] = v;
+        if (k >= 0 && k < MC_HEADS) mc->hf[k] = v;
     }
     __device__ __forceinline__ void set_bl(int e, int v) const
     {
         D.cblink[e] = v;
         const int k = e - D.m;
-        if (mc && k >= 0 && k < MC_HEADS) mc->hb[k] = v;
+        if (k >= 0 && k < MC_HEADS) mc->hb[k] = v;
     }
 };
 // the same interface over two plain arrays (row count lists)
@@ -264,10 +263,10 @@ __device__ __forceinline__ void wave_list_unlink_set(const Links &L, const int *
         L.set_bl(gone, gone);
     }
 }
-// pfl (optional): pfl[q] receives the new forward link of element q (for the next search: Mc::pFl)
+// pfl[q] receives the new forward link of element q (for the next search: Mc::pFl)
 template <class Links>
 __device__ __forceinline__ int wave_list_append_set(const Links &L, int nelem, const int *elems, const int *keys, int n, int big,
-                                                    unsigned long long *kg /* KGMAX words of LDS, all zero between calls */, int *pfl = nullptr)
+                                                    unsigned long long *kg /* KGMAX words of LDS, all zero between calls */, int *pfl)
 {
     const int lane = lane_id();
     const int key = lane < n ? keys[lane] : -1;
@@ -303,7 +302,7 @@ __device__ __forceinline__ int wave_list_append_set(const Links &L, int nelem, c
     if (act) {
         L.set_bl(e, prevl >= 0 ? eprev : t);
         L.set_fl(e, nextl >= 0 ? enext : nelem + key);
-        if (pfl) pfl[lane] = nextl >= 0 ? enext : nelem + key;
+        pfl[lane] = nextl >= 0 ? enext : nelem + key;
         if (prevl < 0) L.set_fl(t, e);
         if (nextl < 0) L.set_bl(nelem + key, e);
     }
@@ -527,7 +526,7 @@ __device__ __forceinline__ int mk_walk(const DevGP &D, Sm *sm, Mc *mc)
                 int fl, cb, cl;
                 double cmx;
                 int ps = -1;
-                if (mc && mc->prevValid) {
+                if (mc->prevValid) {
                     ps = hcol_slot(fa, j);
                     if (ps < mc->prevBase || ps >= MC_PREV || fa->tNew[ps] < 0) ps = -1;
                 }
@@ -582,7 +581,7 @@ __device__ __forceinline__ int mk_walk(const DevGP &D, Sm *sm, Mc *mc)
     return 0;
 }
 
-__device__ __forceinline__ void mk_stage(const DevGP &D, Sm *sm, Mc *mc, long long &mcb, int &fb)
+__device__ __forceinline__ void mk_stage(const DevGP &D, Sm *sm, long long &mcb, int &fb)
 {
     const int lane = lane_id();
     Fast *fa = &sm->fa;
@@ -649,7 +648,7 @@ __device__ __forceinline__ bool mk_express(const DevGP &D, Sm *sm, Mc *mc, int &
     int cb, cl, idx = -1;
     double cmx, val = 0.0;
     int ps = -1;
-    if (mc && mc->prevValid) {
+    if (mc->prevValid) {
         ps = hcol_slot(fa, j);
         if (ps < mc->prevBase || ps >= MC_PREV || fa->tNew[ps] < 0) ps = -1;
     }
@@ -705,7 +704,7 @@ __device__ __forceinline__ bool mk_express(const DevGP &D, Sm *sm, Mc *mc, int &
 
 // single: one candidate entry (a column singleton): nothing to reduce
 // key_given >= 0: the reduction was done already (spec_finish)
-__device__ __forceinline__ void mk_pick(const DevGP &D, Sm *sm, Mc *mc, long long mcb, int fb, int nsearched, bool single, long long key_given = -1)
+__device__ __forceinline__ void mk_pick(const DevGP &D, Sm *sm, long long mcb, int fb, int nsearched, bool single, long long key_given = -1)
 {
     const int lane = lane_id();
     Scalars *S = D.s;
@@ -797,10 +796,8 @@ __device__ __forceinline__ void mk_pick(const DevGP &D, Sm *sm, Mc *mc, long lon
             tb = D.cbeg[jq0];
             tl = D.clen[jq0];
             tc = D.ccap[jq0];
-#if !BLU_CFG_BATCH
             tfl = D.cflink.el(jq0); // for the unlink wave: same round trip, one less on its own chain
             tbl = D.cblink.el(jq0);
-#endif
         }
         int gc = 0, gr = 0;
         if (kind == 1 && hr_slot0 >= 1) {
@@ -814,10 +811,8 @@ __device__ __forceinline__ void mk_pick(const DevGP &D, Sm *sm, Mc *mc, long lon
             fa->tB[slot] = tb;
             fa->tL[slot] = tl;
             fa->tC[slot] = tc;
-#if !BLU_CFG_BATCH // (the batch kernel has no unlink wave and no speculative search)
             fa->tFl[slot] = tfl;
             fa->tBl[slot] = tbl;
-#endif
             hcol_insert(fa, jq0, slot);
             if (kind == 1 && lane != wpos) {
                 const int n = tl + nzc - 1;
@@ -834,7 +829,7 @@ __device__ __forceinline__ void mk_pick(const DevGP &D, Sm *sm, Mc *mc, long lon
         if (lane == 0) {
             fa->kind = kind;
             fa->where = wpos;
-            fa->tLnk = BLU_CFG_BATCH ? 0 : 1;
+            fa->tLnk = 1;
         }
         PROF_STAMP(14);
         return;
@@ -954,14 +949,13 @@ __device__ __forceinline__ void mk_pick(const DevGP &D, Sm *sm, Mc *mc, long lon
 
 // the complete search on the current list state.  Returns false if the shape is outside what this path
 // handles (nothing has been modified then; the caller runs the general search).
-template <bool BATCH>
 __device__ __forceinline__ bool markowitz_fast(const DevGP &D, Sm *sm, Mc *mc, long long ew_mcb, int ew_fb)
 {
     Fast *fa = &sm->fa;
     if (lane_id() == 0) fa->kind = 0;
     PROF_STAMP(8);
     int nsr = 0;
-    if (BLU_EARLY && !BATCH && fa->ewValid) { // found and staged while the previous pivot was being finished (early_search)
+    if (fa->ewValid) { // found and staged while the previous pivot was being finished (early_search)
         const int lane = lane_id();
         const bool whole = fa->ewValid == 2; // a whole search (spec_walk + spec_finish): the winner's key is in spKey
         const long long key = whole ? fa->spKey : -1;
@@ -993,7 +987,7 @@ __device__ __forceinline__ bool markowitz_fast(const DevGP &D, Sm *sm, Mc *mc, l
             if (whole || !mk_express(D, sm, mc, nsr2)) {
                 const int r2 = mk_walk(D, sm, mc);
                 if (r2 == 0) {
-                    mk_stage(D, sm, mc, mcb2, fb2);
+                    mk_stage(D, sm, mcb2, fb2);
                     nsr2 = fa->ncand;
                 } else {
                     okc = false;
@@ -1026,13 +1020,13 @@ __device__ __forceinline__ bool markowitz_fast(const DevGP &D, Sm *sm, Mc *mc, l
 #endif
         PROF_STAMP(9);
         PROF_STAMP(10);
-        mk_pick(D, sm, mc, mcb, fb, nsr, true, key);
+        mk_pick(D, sm, mcb, fb, nsr, true, key);
         return true;
     }
     if (mk_express(D, sm, mc, nsr)) {
         PROF_STAMP(9);
         PROF_STAMP(10);
-        mk_pick(D, sm, mc, 0, 0, nsr, true);
+        mk_pick(D, sm, 0, 0, nsr, true);
         return true;
     }
     const int r = mk_walk(D, sm, mc);
@@ -1041,9 +1035,9 @@ __device__ __forceinline__ bool markowitz_fast(const DevGP &D, Sm *sm, Mc *mc, l
     if (r != 0) return true; // empty column chosen, or error raised
     long long mcb;
     int fb;
-    mk_stage(D, sm, mc, mcb, fb);
+    mk_stage(D, sm, mcb, fb);
     PROF_STAMP(10); // candidate entries + their row metadata loaded and costed
-    mk_pick(D, sm, mc, mcb, fb, fa->ncand, false);
+    mk_pick(D, sm, mcb, fb, fa->ncand, false);
     return true;
 }
 
@@ -1172,7 +1166,7 @@ __device__ __forceinline__ void fast_col(const DevGP &D, Sm *sm, Mc *mc, int q, 
         if (q < 64) { // new begin and maximum: the (early) search of the next pivot reads them
             fa->tB[q] = dst;
             fa->tMx[q] = cmx;
-            if (mc) mc->e1i[q] = -1;
+            mc->e1i[q] = -1;
         }
         fa->tX[q] = xrj;
         fa->tM[q] = mask;
@@ -1273,7 +1267,7 @@ __device__ __forceinline__ void fast_col_short(const DevGP &D, Sm *sm, Mc *mc, i
         if (q < 64) {
             fa->tB[q] = dst;
             fa->tMx[q] = cmx;
-            if (mc) mc->e1i[q] = -1;
+            mc->e1i[q] = -1;
         }
         fa->tX[q] = xrj;
         fa->tM[q] = mask;
@@ -1286,7 +1280,7 @@ __device__ __forceinline__ void fast_col_short(const DevGP &D, Sm *sm, Mc *mc, i
 
 // kind 1: row p of the pivot column, ONE wave.  Appends the whole pivot-row pattern; positions
 // cancelled by fast_col are removed afterwards by fast_fixrow.
-__device__ __forceinline__ void fast_row(const DevGP &D, Sm *sm, Mc *mc, int p, int j_first, int pc, int rnz1)
+__device__ __forceinline__ void fast_row(const DevGP &D, Sm *sm, int p, int j_first, int pc, int rnz1)
 {
     const int lane = lane_id();
     Scalars *S = D.s;
@@ -1357,7 +1351,7 @@ __device__ __forceinline__ bool hcol_has2(const Fast *f, int k)
     if (!(h0 || e0 || h1 || e1)) r = hcol_has(f, k);
     return r;
 }
-__device__ __forceinline__ void fast_row_short(const DevGP &D, Sm *sm, Mc *mc, int p, int j, int pc, int rnz1)
+__device__ __forceinline__ void fast_row_short(const DevGP &D, Sm *sm, int p, int j, int pc, int rnz1)
 {
     const int lane = lane_id();
     Scalars *S = D.s;
@@ -1402,7 +1396,7 @@ __device__ __forceinline__ void fast_row_short(const DevGP &D, Sm *sm, Mc *mc, i
 // single updates with loads that were not issued ahead, and the per-lane selects of the pair set-up cost what the
 // shared instruction stream saves.  Not kept.)
 // rewrite the appended part of row p without the cancelled positions (pivot.rs:752-758)
-__device__ __forceinline__ void fast_fixrow(const DevGP &D, Sm *sm, Mc *mc, int p)
+__device__ __forceinline__ void fast_fixrow(const DevGP &D, Sm *sm, int p)
 {
     const int lane = lane_id();
     Fast *fa = &sm->fa;
@@ -1507,7 +1501,7 @@ __device__ __forceinline__ void early_search(const DevGP &D, Sm *sm, Mc *mc, con
     const int m = D.m;
     Fast *fa = &sm->fa;
     const int K = D.maxsearch;
-    if (!BLU_EARLY || D.search_rows || D.no_fast || K < 1 || K > KCMAX || m >= (1 << 27) || n >= 64) return;
+    if (D.search_rows || D.no_fast || K < 1 || K > KCMAX || m >= (1 << 27) || n >= 64) return;
     if (sm->flag_small || fa->anycancel) return;
     const int left = m - (sm->rank + 1) - sm->rankdef; // active columns at the next search
     if (left < 1) return;
@@ -1535,7 +1529,7 @@ __device__ __forceinline__ void early_search(const DevGP &D, Sm *sm, Mc *mc, con
             cmx = maxs[l];
             // a column of two that lost its pivot-row entry: the wave that updated it left the entry that stays and
             // the metadata of its row in LDS (fast_scol): no round trip at all
-            if (mc && ebase + l < MC_PREV && mc->e1i[ebase + l] >= 0 && mc->e1rl[ebase + l] >= 0) fs = ebase + l;
+            if (ebase + l < MC_PREV && mc->e1i[ebase + l] >= 0 && mc->e1rl[ebase + l] >= 0) fs = ebase + l;
         }
         if (j >= 0) {
             if (cmx == 0.0 || !(cmx >= D.abstol)) return;
@@ -1623,7 +1617,7 @@ __device__ __forceinline__ void spec_walk(const DevGP &D, Sm *sm, Mc *mc)
     Fast *fa = &sm->fa;
     const int K = D.maxsearch;
     if (lane == 0) fa->spOk = 0;
-    if (!mc || D.no_fast || K < 1 || K > KCMAX || m >= (1 << 27)) return;
+    if (D.no_fast || K < 1 || K > KCMAX || m >= (1 << 27)) return;
     if (m - (sm->rank + 1) - sm->rankdef < K) return;
     const LinksC LC{D, mc};
     if (LC.fl(m) != m) return;
@@ -1809,7 +1803,6 @@ __device__ __forceinline__ void spec_finish(const DevGP &D, Sm *sm, int n)
 // ------------------------------------------------------------------------------------------------
 // kind 1, whole workgroup
 // ------------------------------------------------------------------------------------------------
-template <bool BATCH>
 __device__ __forceinline__ void fast_small(const DevGP &D, Sm *sm, Mc *mc, int pr, int pc, int nzc, int nzr, long long &ew_mcb, int &ew_fb)
 {
     const int w = wave_id(), nw = num_waves(), lane = lane_id();
@@ -1826,21 +1819,20 @@ __device__ __forceinline__ void fast_small(const DevGP &D, Sm *sm, Mc *mc, int p
     // round the waves in reverse: the waves that got the last columns get no second column.
     const int ntask = rnz1 + cnz1;
     PROF_STAMP(4);
-    // With 8 or more waves (the single-matrix configuration; a 4-wave batch workgroup cannot spare one) the
-    // last wave does not take line updates: it unlinks the columns of the pivot row from their count lists
-    // meanwhile (their new lists are known only after the updates: the append
+    // With 8 or more waves the last wave does not take line updates: it unlinks the columns of the pivot row
+    // from their count lists meanwhile (their new lists are known only after the updates: the append
     // half follows in the finalize step).
-    const bool split = !BATCH && nw >= 8 && rnz1 < 64;
+    const bool split = nw >= 8 && rnz1 < 64;
     const int nwt = split ? nw - 1 : nw;
     const LinksC LC{D, mc};
-    const bool early = BLU_EARLY && split && !D.search_rows;
+    const bool early = split && !D.search_rows;
     if (split && w == nw - 1) {
         // this wave's chain of dependent loads is the longest thing in the phase and it issues few instructions:
         // it goes first on its SIMD
-        if (early && BLU_SPEC) __builtin_amdgcn_s_setprio(3);
+        if (early) __builtin_amdgcn_s_setprio(3);
         const bool lnk = fa->tLnk != 0; // (elems = tJ + 1: staged links from slot 1, the pivot column's at slot 0 = index -1)
         wave_list_unlink_set(LC, fa->tJ + 1, rnz1, -1, InHCol{fa, 1, 0}, pc, lnk ? fa->tFl + 1 : nullptr, lnk ? fa->tBl + 1 : nullptr, -1);
-        if (early && BLU_SPEC) {
+        if (early) {
             wave_mem_sync();
             spec_walk(D, sm, mc);
             __builtin_amdgcn_s_setprio(0);
@@ -1893,8 +1885,8 @@ __device__ __forceinline__ void fast_small(const DevGP &D, Sm *sm, Mc *mc, int p
                 if (ll[u] <= 64) fast_col_short(D, sm, mc, t + 1, work, li[u], lv[u], pr, cnz1, pivot);
                 else fast_col(D, sm, mc, t + 1, work, li[u], lv[u], pr, cnz1, pivot);
             } else if (t < ntask) {
-                if (ll[u] <= 64) fast_row_short(D, sm, mc, t - rnz1 + 1, li[u], pc, rnz1);
-                else fast_row(D, sm, mc, t - rnz1 + 1, li[u], pc, rnz1);
+                if (ll[u] <= 64) fast_row_short(D, sm, t - rnz1 + 1, li[u], pc, rnz1);
+                else fast_row(D, sm, t - rnz1 + 1, li[u], pc, rnz1);
             }
 #ifdef BLU_PROFILE
             if (w == 1 && base == 0) PROF_STAMP_L0(35 + u);
@@ -1911,13 +1903,13 @@ __device__ __forceinline__ void fast_small(const DevGP &D, Sm *sm, Mc *mc, int p
     __syncthreads();
     PROF_STAMP(3);
     if (fa->anycancel) {
-        for (int p = 1 + w; p <= cnz1; p += nw) fast_fixrow(D, sm, mc, p);
+        for (int p = 1 + w; p <= cnz1; p += nw) fast_fixrow(D, sm, p);
         __syncthreads();
     }
     // finalize step, one job per wave: [0] the search of the NEXT pivot (early_search), [1] L column,
     // [2] count lists, [3] U row and the pivot's own bookkeeping; with fewer than 4 waves (or row search)
     // wave 0 writes the U row instead and the next search waits for the barrier
-    const bool spec = BLU_SPEC && early && (w == 0 || w == nw - 1) && spec_cond(sm, fa->tNew + 1, rnz1);
+    const bool spec = early && (w == 0 || w == nw - 1) && spec_cond(sm, fa->tNew + 1, rnz1);
     if (w == 0 && early && !spec) early_search(D, sm, mc, fa->tJ + 1, fa->tNew + 1, fa->tB + 1, fa->tMx + 1, rnz1, 1, ew_mcb, ew_fb);
     if (w == nw - 1 && spec) spec_finish(D, sm, rnz1);
     if (w == (early ? 3 : 0)) {
@@ -1936,10 +1928,10 @@ __device__ __forceinline__ void fast_small(const DevGP &D, Sm *sm, Mc *mc, int p
     }
     if (w == 2 % nw) {
         PROF_STAMP_L0(25);
-        const int mn = split ? wave_list_append_set(LC, m, fa->tJ + 1, fa->tNew + 1, rnz1, m + 2, fa->kg[0], mc ? mc->pFl + 1 : nullptr)
+        const int mn = split ? wave_list_append_set(LC, m, fa->tJ + 1, fa->tNew + 1, rnz1, m + 2, fa->kg[0], mc->pFl + 1)
                              : wave_list_move_batch_set(LC, m, fa->tJ + 1, fa->tNew + 1, rnz1, InHCol{fa, 1, 0}, m + 2, pc, fa->kg[0]);
         if (lane == 0 && mn < sm->min_colnz) sm->min_colnz = mn;
-        if (mc && lane == 0) {
+        if (lane == 0) {
             mc->prevValid = split ? 1 : 0;
             mc->prevBase = 1;
         }
@@ -1964,7 +1956,6 @@ __device__ __forceinline__ void fast_small(const DevGP &D, Sm *sm, Mc *mc, int p
 // dependent look-ups of the search 3 300, stores and bookkeeping 1 800 -- cost the 6.8 us that the sixteen-wave
 // route with its three barriers costs: 820 -> 885 ms at C3.  Not kept.)
 // ------------------------------------------------------------------------------------------------
-template <bool BATCH>
 __device__ __forceinline__ void fast_scol(const DevGP &D, Sm *sm, Mc *mc, int pr, int pc, int rl, int wq, long long &ew_mcb, int &ew_fb)
 {
     const int w = wave_id(), nw = num_waves(), lane = lane_id();
@@ -1975,7 +1966,7 @@ __device__ __forceinline__ void fast_scol(const DevGP &D, Sm *sm, Mc *mc, int pr
 
     // (as in fast_small: with 8 or more waves the last one unlinks the row's columns from their count lists
     // while the others take the column updates)
-    const bool split = !BATCH && nw >= 8 && rl < 64;
+    const bool split = nw >= 8 && rl < 64;
     const int nwt = split ? nw - 1 : nw;
     const LinksC LC{D, mc};
     if (split && w == nw - 1) {
@@ -2000,7 +1991,7 @@ __device__ __forceinline__ void fast_scol(const DevGP &D, Sm *sm, Mc *mc, int pr
             // the one entry that stays in a column of two: the column is a singleton now, very likely the next pivot
             // column.  The next search finds the entry in LDS, and the metadata of its row as well: loaded here, by
             // the one lane that holds the entry (rows do not change in a singleton-column pivot), stored at the end.
-            const bool fw1 = mc && cl == 2 && q < MC_PREV && v && lane != src;
+            const bool fw1 = cl == 2 && q < MC_PREV && v && lane != src;
             int f_rb = 0, f_rl = 0, f_rc = 0;
             if (fw1) {
                 f_rb = D.rbeg[idx];
@@ -2026,7 +2017,7 @@ __device__ __forceinline__ void fast_scol(const DevGP &D, Sm *sm, Mc *mc, int pr
                 D.colmax[j] = cmx;
                 fa->tNew[q] = cl - 1;
                 if (q < 64) fa->tMx[q] = cmx;
-                if (mc && cl != 2 && q < MC_PREV) mc->e1i[q] = -1;
+                if (cl != 2 && q < MC_PREV) mc->e1i[q] = -1;
                 fa->tX[q] = xrj;
                 if (cmx == 0.0 || cmx < D.abstol) sm->flag_small = 1;
             }
@@ -2053,7 +2044,7 @@ __device__ __forceinline__ void fast_scol(const DevGP &D, Sm *sm, Mc *mc, int pr
             if (v && idx != pr) {
                 const double x = fabs(val);
                 if (x > cmxl) cmxl = x;
-                if (mc && cl == 2 && q < MC_PREV) { // (never here: a column of two takes the short form above)
+                if (cl == 2 && q < MC_PREV) { // (never here: a column of two takes the short form above)
                     mc->e1i[q] = idx;
                     mc->e1v[q] = val;
                     mc->e1rl[q] = -1;
@@ -2069,14 +2060,14 @@ __device__ __forceinline__ void fast_scol(const DevGP &D, Sm *sm, Mc *mc, int pr
             D.colmax[j] = cmx;
             fa->tNew[q] = cl - 1;
             if (q < 64) fa->tMx[q] = cmx;
-            if (mc && cl != 2 && q < MC_PREV) mc->e1i[q] = -1;
+            if (cl != 2 && q < MC_PREV) mc->e1i[q] = -1;
             fa->tX[q] = xrj;
             if (cmx == 0.0 || cmx < D.abstol) sm->flag_small = 1;
         }
     }
     __syncthreads();
     // finalize step: [0] the search of the next pivot, [1] count lists, [2] U row and bookkeeping
-    const bool early = BLU_EARLY && split && !D.search_rows;
+    const bool early = split && !D.search_rows;
     if (w == 0 && early) early_search(D, sm, mc, fa->tJ, fa->tNew, fa->tB, fa->tMx, rl, 0, ew_mcb, ew_fb);
     if (w == (early ? 2 : 0)) {
         fast_write_u(D, sm, 0, rl - 1, wq);
@@ -2091,10 +2082,10 @@ __device__ __forceinline__ void fast_scol(const DevGP &D, Sm *sm, Mc *mc, int pr
     if (w == 1 % nw) {
         if (D.search_rows && lane == 0) list_remove1(D.rflink, D.rblink, pr);
         // the pivot column sits at slot `where` of the row with key -1: it is unlinked as `gone`
-        const int mn = split ? wave_list_append_set(LC, m, fa->tJ, fa->tNew, rl, m + 2, fa->kg[0], mc ? mc->pFl : nullptr)
+        const int mn = split ? wave_list_append_set(LC, m, fa->tJ, fa->tNew, rl, m + 2, fa->kg[0], mc->pFl)
                              : wave_list_move_batch_set(LC, m, fa->tJ, fa->tNew, rl, InHCol{fa, 0, wq}, m + 2, pc, fa->kg[0]);
         if (lane == 0 && mn < sm->min_colnz) sm->min_colnz = mn;
-        if (mc && lane == 0) { // what the next search may reuse (a column that sank below abstol cancels it: dirty)
+        if (lane == 0) { // what the next search may reuse (a column that sank below abstol cancels it: dirty)
             mc->prevValid = split ? 1 : 0;
             mc->prevBase = 0;
         }

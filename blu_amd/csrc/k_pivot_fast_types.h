@@ -1,29 +1,7 @@
 // k_pivot_fast_types.h -- LDS working set of the low-latency pivot paths (see k_pivot_fast.hip)
-// (no include guard: k_pivot.hip includes this once per configuration, inside its namespace)
-#undef PCMAX
-#undef PRMAX
-#undef STGMAX
-#undef KCMAX
-#undef HROW
-#undef HCOL
-#undef KGMAX
-#undef HROW_BITS
-#undef HCOL_BITS
-#undef MC_HEADS
-#undef MC_PREV
+// (included once, by the single-matrix configuration of k_pivot.hip, inside its namespace)
 #define PCMAX 65    // cached pivot column entries (pivot_small: <= 64 off-diagonals)
 #define KCMAX 4     // candidate columns handled by the flattened search (maxsearch <= KCMAX)
-#if BLU_CFG_BATCH
-// batch configuration: pivot rows up to 64 entries (all of them on the banded LP bases; longer rows take the
-// general paths), hash tables at half load for that, ~11 KB of LDS per workgroup instead of ~24 KB
-#define PRMAX 64
-#define STGMAX 80
-#define HROW 128
-#define HCOL 128
-#define KGMAX 64
-#define HROW_BITS 7
-#define HCOL_BITS 7
-#else
 #define PRMAX 256   // cached pivot row entries
 #define STGMAX 104  // staged Markowitz candidate entries
 #define HROW 256    // hash slots, rows of the pivot column (<= 64 keys)
@@ -31,20 +9,8 @@
 #define KGMAX 128   // batched list moves: keys (new counts) below this meet in an LDS table
 #define HROW_BITS 8
 #define HCOL_BITS 9
-#endif
-// Early search (early_search in k_pivot_fast.hip): when the next pivot is a column singleton, wave 0 finds
-// and stages it while the other waves write out the current pivot.  -DBLU_EARLY=0 switches it off; `make
-// ewcheck` builds a library that verifies every early result against the ordinary search.
-#ifndef BLU_EARLY
-#define BLU_EARLY 1
-#endif
-// Speculative search (spec_walk / spec_finish in k_pivot_fast.hip): the search of the next pivot beside the line
-// updates and the finalize step of a kind-1 pivot.  -DBLU_SPEC=0 switches it off.
-#ifndef BLU_SPEC
-#define BLU_SPEC 1
-#endif
 
-// ---- list heads of the single-matrix kernel in LDS (k_pivot_loop; the batch kernel has none) ---------------
+// ---- list heads in LDS ------------------------------------------------------------------------------------
 // Heads and tails of the column count lists 0..MC_HEADS-1 (cflink/cblink[m + k]) live in LDS: every search
 // starts at them and every batched list update ends at them, so each pivot saves two dependent global round
 // trips.  WRITE-THROUGH: global memory is always current.  Everything the general pivot paths do goes straight
@@ -88,11 +54,7 @@ struct Fast {
     double pcV[PCMAX];
     // pivot row, pivot column at slot 0 (kind 1), with the (begin,len,cap) of each column
     int tJ[PRMAX], tB[PRMAX], tL[PRMAX], tC[PRMAX], tNew[PRMAX];
-#if BLU_CFG_BATCH
-    int tFl[1], tBl[1], tLnk; // (single-matrix kernel only)
-#else
     int tFl[64], tBl[64], tLnk; // tLnk: the count-list links of the row's columns (slots < 64) were loaded with their metadata
-#endif
     double tX[PRMAX]; // pivot-row value of the column
     unsigned long long tM[PRMAX];
     // staged candidate entries

@@ -4,7 +4,7 @@
 // Reference: factorize_bump (src/lu/factorize_bump.rs:12-49), markowitz (src/lu/markowitz.rs:34-123),
 // pivot_small (src/lu/pivot.rs:460-833), pivot_singleton_col (:928-1025), list_move (src/lu/list.rs:89-99).
 //
-// Why: the four-wave workgroups of k_pivot_loop_batch keep three waves waiting while one searches, and give every
+// Why: the four-wave workgroups of the earlier batch kernel kept three waves waiting while one searched, and gave every
 // line of a pivot a whole wave (a 20-entry column uses 20 of 64 lanes for ~270 vector instructions).  A batch is
 // bound by the instruction issue of the CUs, so this kernel (a) runs a matrix on a single wave -- no workgroup
 // barrier, every resident wave is an active instruction stream -- and (b) packs the lines of a pivot into the lanes:
@@ -212,20 +212,17 @@ __device__ __forceinline__ int wv_list_move(const DevGP &D, Fast *fa, int e, int
 // ------------------------------------------------------------------------------------------------
 // The list walk of a search (markowitz.rs:73-123: the first maxsearch columns in count-list order) as a resumable
 // sequence of steps, one memory round trip each: the list heads, then link + metadata of one candidate column at a
-// time.  A search runs the steps back to back.  A pivot_small STARTS the walk of the NEXT search as soon as its own
-// list move is done (lists and column metadata are final then, unless a column has to be removed) and advances it
-// one step at each stage of the rest of its work -- row epilogue, row append, L column, clean-up, pivot record --
-// so that the next search finds its candidates waiting: the walk is the longest dependent chain of a search.
+// time.  A search runs the steps back to back.  The two-wave kernel STARTS the walk of the NEXT search as soon as
+// a pivot_small has done its list move (k_pivot_wave2.inc), so that the next search finds its candidates waiting:
+// the walk is the longest dependent chain of a search.
 // ------------------------------------------------------------------------------------------------
-// MEASURED (round 3, MI355X): with the early start the walk disappears from the search (7 240 -> 1 070 ticks per search)
-// but every stage that advances it gets ~2 000 ticks slower, and the pivot kernel as a whole 7 % slower (C2: 0.146 ->
-// 0.156 s at 1024 bases, C3: 2.10 -> 2.23 s at 1536): a step has to wait for its loads with s_waitcnt vmcnt, and on
-// gfx950 loads and stores share that in-order counter -- the wait also drains the scattered stores the stage before
-// has just issued, which nothing waits for otherwise.  So the early start is OFF (WV_EARLY_WALK 0); a search runs the
-// steps back to back.
-#ifndef WV_EARLY_WALK
-#define WV_EARLY_WALK 0
-#endif
+// MEASURED (round 3, MI355X): the one-wave kernel with the same early start, advanced one step at each stage of the
+// rest of the pivot (row epilogue, row append, L column, clean-up, pivot record): the walk disappears from the search
+// (7 240 -> 1 070 ticks per search) but every stage that advances it gets ~2 000 ticks slower, and the pivot kernel as
+// a whole 7 % slower (C2: 0.146 -> 0.156 s at 1024 bases, C3: 2.10 -> 2.23 s at 1536): a step has to wait for its
+// loads with s_waitcnt vmcnt, and on gfx950 loads and stores share that in-order counter -- the wait also drains the
+// scattered stores the stage before has just issued, which nothing waits for otherwise.  So the one-wave kernel has
+// no early start.
 struct WvWalk {
     int st;     // 0 idle, 1 list heads in flight, 2 a candidate in flight, 3 done: candidates in fa->c*, 4 not handled here (the
                 // general search decides), 5 an empty column heads list 0, 6 a column singleton heads list 1
@@ -315,9 +312,6 @@ __device__ __forceinline__ void ew_step(const DevGP &D, Sm *sm, WvWalk &E, int K
 #if WV_NW == 2
 // Two waves per matrix: what the search (wave 0) found goes to LDS for both waves -- the metadata of every line of the
 // pivot, both membership tables, and which lines each wave takes (by weight: entries to read + entries to append).
-#ifndef WV2_SHARE0
-#define WV2_SHARE0 50 // percent of the columns' weight wave 0 takes (wave 1 then has all the rows)
-#endif
 __device__ __forceinline__ void wv2_publish(Fast *fa, const WvLines &L, int rnz1, int cnz1)
 {
     const int lane = lane_id();
@@ -343,7 +337,8 @@ __device__ __forceinline__ void wv2_publish(Fast *fa, const WvLines &L, int rnz1
     // a line goes to wave 0 if it BEGINS inside wave 0's share (the first line always does)
     int tc;
     const int cw = wv_excl_scan(lane < rnz1 ? L.cl + cnz1 : 0, &tc);
-    const int cs = __popcll(__ballot(lane < rnz1 && (long long)cw * 100 < (long long)tc * WV2_SHARE0));
+    // wave 0 takes half the columns' weight (wave 1 then has all the rows)
+    const int cs = __popcll(__ballot(lane < rnz1 && (long long)cw * 100 < (long long)tc * 50));
     if (lane == 0) {
         fa->csplit = cs;
         fa->tiny = 0;
@@ -953,14 +948,7 @@ __device__ __forceinline__ void wv_small(const DevGP &D, Sm *sm, const WvLines &
     // pivot-row order; the pivot column leaves.  (Here, not at the end: the tails arrived during the rows pass, and
     // from here on the lists are final -- the walk of the next search can start.)
     const int mn = wv_list_move(D, fa, L.j, newlen, lane < rnz1, lane == rnz1, L.fl, L.bl, rnz1, D.m + 2, ltail);
-    {
-        const int K = D.maxsearch;
-        E.st = 0;
-        if (WV_EARLY_WALK && !tinyb && D.search_rows == 0 && !D.no_fast && K >= 1 && K <= KCMAX) { // (a column to be removed would change the lists again)
-            const int cur = sm->min_colnz;
-            ew_begin(D, E, mn < cur ? mn : cur);
-        }
-    }
+    E.st = 0;
     WV_T(17);
     int rnk = 0, rdst = L.rb, rnewcap = L.rc;
     int rused = sm->rused;
@@ -991,7 +979,6 @@ __device__ __forceinline__ void wv_small(const DevGP &D, Sm *sm, const WvLines &
         if (lane < cnz1) fa->sDst[lane] = rdst + rnk;
     }
     wave_mem_sync();
-    if (WV_EARLY_WALK && (E.st == 1 || E.st == 2)) ew_step(D, sm, E, D.maxsearch);
     WV_T(13);
     // ---- append the pattern of the pivot row, minus the cancelled positions (pivot.rs:752-758): (row, position) pairs
     int rnew = rnk + rnz1;
@@ -1026,7 +1013,6 @@ __device__ __forceinline__ void wv_small(const DevGP &D, Sm *sm, const WvLines &
         D.rcap[L.i] = rnewcap;
     }
 
-    if (WV_EARLY_WALK && (E.st == 1 || E.st == 2)) ew_step(D, sm, E, D.maxsearch);
     WV_T(14);
     // ---- L column (pivot.rs:778-790)
     double lx = 0.0;
@@ -1045,7 +1031,6 @@ __device__ __forceinline__ void wv_small(const DevGP &D, Sm *sm, const WvLines &
 #endif
 
     WV_T(15);
-    if (WV_EARLY_WALK && (E.st == 1 || E.st == 2)) ew_step(D, sm, E, D.maxsearch);
     WV_T(16);
     // ---- cleanup (pivot.rs:792-800)
     WAVE_LOCKSTEP(); // (every lane has read sm->lused above before lane 0 replaces it)
@@ -1069,7 +1054,6 @@ __device__ __forceinline__ void wv_small(const DevGP &D, Sm *sm, const WvLines &
     const int d3all = wave_sum_i(nd3);
     if (lane == 0 && d3all) sm->d3 += d3all;
     wave_mem_sync();
-    if (WV_EARLY_WALK && (E.st == 1 || E.st == 2)) ew_step(D, sm, E, D.maxsearch);
     WV_T(16);
 }
 #endif // WV_NW == 1
@@ -1360,7 +1344,6 @@ __device__ __forceinline__ void pivot_loop_wave(DevLU *Ds, int stop_at, Sm *sm)
         }
         rank++;
         wave_mem_sync();
-        if (WV_EARLY_WALK && (E.st == 1 || E.st == 2)) ew_step(D, sm, E, D.maxsearch);
         WV_T(22);
     }
     wave_mem_sync();
@@ -1390,10 +1373,8 @@ __device__ __forceinline__ void pivot_loop_wave(DevLU *Ds, int stop_at, Sm *sm)
     }
 }
 
-#ifndef BLU_WAVE_OCC
-#define BLU_WAVE_OCC 4 // waves per SIMD the register budget is set for
-#endif
-__global__ void __launch_bounds__(64) BLU_WAVES_PER_EU(BLU_WAVE_OCC, BLU_WAVE_OCC) k_pivot_loop_wave(DevLU *Ds, int stop_at)
+// register budget: four waves per SIMD
+__global__ void __launch_bounds__(64) BLU_WAVES_PER_EU(4, 4) k_pivot_loop_wave(DevLU *Ds, int stop_at)
 {
     __shared__ Sm smem;
     pivot_loop_wave(Ds, stop_at, &smem);

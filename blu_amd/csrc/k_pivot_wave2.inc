@@ -24,9 +24,6 @@
 // Arena positions of re-appended lines come from an LDS atomic, so WHERE a re-appended line lands depends on which
 // wave asks first; the totals (and with them every room check, every compaction, every result) do not.
 
-#ifndef WV2_EARLY_WALK
-#define WV2_EARLY_WALK 1
-#endif
 __device__ __forceinline__ void wv2_small(const DevGP &D, Sm *sm, WvWalk &E, int pr, int pc, int nz_col, int nz_row)
 {
     const int lane = lane_id(), w = wave_id();
@@ -305,7 +302,7 @@ __device__ __forceinline__ void wv2_small(const DevGP &D, Sm *sm, WvWalk &E, int
         // ---- the list walk of the NEXT search (see WvWalk): lists and column metadata are final (unless a column has
         // to be removed, which changes the lists again); it runs while wave 1 updates the rows
         const int K = D.maxsearch;
-        if (WV2_EARLY_WALK && !fa->tiny && D.search_rows == 0 && !D.no_fast && K >= 1 && K <= KCMAX) ew_begin(D, E, sm->min_colnz);
+        if (!fa->tiny && D.search_rows == 0 && !D.no_fast && K >= 1 && K <= KCMAX) ew_begin(D, E, sm->min_colnz);
     }
     // ================= row file update (pivot.rs:695-775): wave 1, all the rows =================
     // (MEASURED, C3 x 1536: starting the rows BEFORE B2 -- the overlap with the pivot row leaves every row whatever the
@@ -612,10 +609,8 @@ __device__ __forceinline__ void pivot_loop_wave2(DevLU *Ds, int stop_at, Sm *sm)
     }
 }
 
-#ifndef BLU_WAVE2_OCC
-#define BLU_WAVE2_OCC 4 // waves per SIMD the register budget is set for
-#endif
-__global__ void __launch_bounds__(128) BLU_WAVES_PER_EU(BLU_WAVE2_OCC, BLU_WAVE2_OCC) k_pivot_loop_wave2(DevLU *Ds, int stop_at)
+// register budget: four waves per SIMD
+__global__ void __launch_bounds__(128) BLU_WAVES_PER_EU(4, 4) k_pivot_loop_wave2(DevLU *Ds, int stop_at)
 {
     __shared__ Sm smem;
     pivot_loop_wave2(Ds, stop_at, &smem);

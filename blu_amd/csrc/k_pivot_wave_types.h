@@ -22,10 +22,7 @@
 #define WV_HASH 128   // hash slots: <= 64 keys, at most half full
 #define WV_ZW 64      // zero-words: segment-head bits of a flattened pass / key groups of a list move
 #define WV_TMAX (64 * WV_ZW) // entries of all lines of one flattened phase
-#ifndef WV_WCAP_SET
-#define WV_WCAP_SET (256 * WV_NW)
-#endif
-#define WV_WCAP WV_WCAP_SET // old values of the entries being updated, columns of one group x pivot-column positions
+#define WV_WCAP (256 * WV_NW) // old values of the entries being updated, columns of one group x pivot-column positions
 #define WV_WHALF (WV_WCAP / 2) // ... of which each wave of the two-wave kernel has one half
 #define WV_STG 128    // entries of the candidate columns of one search
 #define KCMAX 4       // candidate columns of a search (maxsearch <= KCMAX)

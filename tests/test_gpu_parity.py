@@ -496,7 +496,7 @@ def test_bucket_fill_rows_of_every_length_and_duplicates(blu, oracle, monkeypatc
 
 @pytest.mark.parametrize("spec", [(3000, 9, 10, 0.4, 17, 0.4), (2500, 10, 9, 0.5, 1, 0.3), (1800, 6, 30, 0.1, 9, 1.0)],
                          ids=["mixed", "c3-like", "wide-band"])
-def test_one_wave_kernel_matches_workgroup_kernel_and_oracle(blu, oracle, spec):
+def test_wave_kernels_match_workgroup_kernel_and_oracle(blu, oracle, spec):
     """A/B/C of the pivot kernels on one basis -- k_pivot_loop_wave (one wave per matrix, flattened line updates) and
     k_pivot_loop_wave2 (the same passes dealt out to two waves; the walk of the next search begun early), the kernels
     of a batch, against k_pivot_loop (sixteen waves) -- and all against the oracle; the flattened paths must have
@@ -505,11 +505,14 @@ def test_one_wave_kernel_matches_workgroup_kernel_and_oracle(blu, oracle, spec):
     m = spec[0]
     a, b, c2 = blu.BLU(m, len(ri)), blu.BLU(m, len(ri)), blu.BLU(m, len(ri))
     a.dbg_set_pivot_kernel(1)
-    b.dbg_set_pivot_kernel(2)
+    b.dbg_set_pivot_kernel(0)
     c2.dbg_set_pivot_kernel(3)
+    with pytest.raises(blu.BluError):  # (2 was the retired four-wave batch kernel)
+        b.dbg_set_pivot_kernel(2)
     sa, sb, sc = (h.factorize(cp[:-1], cp[1:], ri, v) for h in (a, b, c2))
     o, so = util.oracle_factorize(oracle, cp, ri, v, allow_d3=True)
     assert sa == sb == sc == so == K.OK
+    assert (a.stat(118), b.stat(118), c2.stat(118)) == (1, 0, 3)
     fa, fb, fc, fo = a.get_factors(), b.get_factors(), c2.get_factors(), o.get_factors()
     for k in util.INT_KEYS + util.VAL_KEYS:
         assert np.array_equal(fa[k], fb[k]) and np.array_equal(fa[k], fo[k]) and np.array_equal(fc[k], fo[k]), k

@@ -1,6 +1,6 @@
 #!/bin/bash
 # A/B of batch runs on one GPU box: bash tools/batch_env_ab.sh cfg:B:kernel:hintdiv:ENV=VAL,ENV=VAL ...  (one tools/batch_probe.py line each;
-# kernel = BLU_PIVOT_KERNEL, hintdiv = divisor of the capacity hint, ENV = e.g. BLU_BATCH_GRID=128)
+# kernel = BLU_PIVOT_KERNEL (0 default, 1 one-wave, 3 two-wave), hintdiv = divisor of the capacity hint, ENV = e.g. BLU_BATCH_GRID=128)
 R=${GRAFT_REPO_ROOT:-/root/repo}; cd $R
 OUT=gpurun_out/batch_env_ab.log; : > $OUT
 for a in "$@"; do

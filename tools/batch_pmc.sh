@@ -1,12 +1,12 @@
 #!/bin/bash
 # SQ counters of the batch pivot kernel ($2 bases of config $1, default 1280 x C2; $3 = kernel name regex, default
-# k_pivot_loop_batch -- pass k_pivot_loop_wave for the one-wave kernel, k_pivot_loop_wave2 for the two-wave one;
+# k_pivot_loop_wave -- both wave kernels, of which a batch runs one; pass k_pivot_loop_wave2 for the two-wave one alone;
 # $4 = divisor of the capacity hint, default 1, 2 for a batch that fills the card), two passes of 8 counters.
 # rocprofv3 --pmc must not be combined with tracing; the program itself follows "--".
 R=${GRAFT_REPO_ROOT:-/root/repo}
 CFG=${1:-C2}
 NB=${2:-1280}
-KRE=${3:-k_pivot_loop_batch}
+KRE=${3:-k_pivot_loop_wave}
 HD=${4:-1}
 cd /tmp && export TMPDIR=/tmp
 A="SQ_WAVES SQ_WAVE_CYCLES SQ_BUSY_CYCLES SQ_WAIT_ANY SQ_WAIT_INST_ANY SQ_ACTIVE_INST_ANY SQ_ACTIVE_INST_VALU SQ_ACTIVE_INST_LDS"
@@ -22,7 +22,7 @@ tot = collections.defaultdict(float); n = collections.Counter()
 for f in glob.glob(sys.argv[1] + "/gpurun_out/bpmc_*/**/*counter_collection.csv", recursive=True):
     for r in csv.DictReader(open(f)):
         kn = r.get("Kernel_Name", "")
-        if sys.argv[2] in kn and not (sys.argv[2].endswith("_wave") and "_wave2" in kn):
+        if sys.argv[2] in kn:
             tot[r["Counter_Name"]] += float(r["Counter_Value"]); n[r["Counter_Name"]] += 1
 for k in sorted(tot): print("%-22s %.4g per dispatch (%d dispatches)" % (k, tot[k] / n[k], n[k]))
 PY

@@ -47,7 +47,7 @@ for leg in ("single", "C3", "C4", "C2"):
         for f in glob.glob(R + "/gpurun_out/pmc_%s_%s/**/*counter_collection.csv" % (leg, c), recursive=True):
             for r in csv.DictReader(open(f)):
                 kn = r.get("Kernel_Name", "")
-                k = ("k_pivot_loop_wave2" if "k_pivot_loop_wave2" in kn else "k_pivot_loop_wave" if "k_pivot_loop_wave" in kn else "k_pivot_loop_batch" if "k_pivot_loop_batch" in kn
+                k = ("k_pivot_loop_wave2" if "k_pivot_loop_wave2" in kn else "k_pivot_loop_wave" if "k_pivot_loop_wave" in kn
                      else ("k_pivot_loop" if "k_pivot_loop" in kn else None))
                 if k and r["Counter_Name"] == c:
                     vals[k][c].append(float(r["Counter_Value"]))

@@ -35,7 +35,7 @@ h = hs[0]
 tp = h.stat(K.STAT_DEV_TIME_PIVOT_LOOP)
 tot = sum(h.stat(60 + k) for k in range(24))
 npiv = h.stat(52) + h.stat(54)
-print("B=%d %s (%s): pivot kernel %.3f s; basis 0: %.0f ticks in %d pivots (small %d, scol %d; searches handed over %d, with the walk begun early %d)" % (B, cfg, {0: "k_pivot_loop", 1: "k_pivot_loop_wave", 2: "k_pivot_loop_batch", 3: "k_pivot_loop_wave2"}[int(h.stat(118))], tp, tot, npiv, h.stat(54), h.stat(52), h.stat(116), h.stat(117)))
+print("B=%d %s (%s): pivot kernel %.3f s; basis 0: %.0f ticks in %d pivots (small %d, scol %d; searches handed over %d, with the walk begun early %d)" % (B, cfg, {0: "k_pivot_loop", 1: "k_pivot_loop_wave", 3: "k_pivot_loop_wave2"}[int(h.stat(118))], tp, tot, npiv, h.stat(54), h.stat(52), h.stat(116), h.stat(117)))
 for k, nm in enumerate(names):
     t, n = h.stat(60 + k), h.stat(84 + k)
     if n:
