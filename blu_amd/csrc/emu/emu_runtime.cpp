@@ -7,6 +7,7 @@
 #define EMU_ASAN 1
 extern "C" void __sanitizer_start_switch_fiber(void **fake_stack_save, const void *bottom, size_t size);
 extern "C" void __sanitizer_finish_switch_fiber(void *fake_stack_save, const void **bottom_old, size_t *size_old);
+extern "C" void __asan_unpoison_memory_region(void const volatile *addr, size_t size);
 #endif
 #endif
 
@@ -168,6 +169,14 @@ void launch(dim3 grid, dim3 block, const std::function<void()> &body)
             F.ctx.uc_stack.ss_size = kStack;
             F.ctx.uc_link = nullptr;
             makecontext(&F.ctx, (void (*)())fiber_main, 0);
+#ifdef EMU_ASAN
+            // The sanitizer's swapcontext clears the shadow of the WHOLE stack the context names, on every switch: 64 KB of
+            // shadow per collective and lane, several times the cost of the kernels themselves.  The switches are announced
+            // (start / finish_switch_fiber), so all that is needed is a clean stack once per launch -- the frames of the
+            // previous launch's fiber were never unwound -- and a context that no longer names its stack.
+            __asan_unpoison_memory_region(F.stack, kStack);
+            F.ctx.uc_stack.ss_size = 0;
+#endif
         }
         g_blk = &B;
         memset(g_hcount, 0, sizeof g_hcount);

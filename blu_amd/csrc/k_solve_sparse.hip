@@ -141,6 +141,7 @@ __device__ __forceinline__ int dfs_reach_wave(const G &g, int i0, int top, int *
     const int lane = lane_id();
     int head = 0, lo = 0; // ring slots of the levels lo..head-1 are valid
     int i = i0, p = g.begin(i0), e = g.end(i0);
+    WAVE_LOCKSTEP(); // (the caller's lanes have all looked at marked[i0] before lane 0 sets it)
     if (lane == 0) {
         marked[i0] = M;
         xi[0] = i0;
@@ -195,6 +196,7 @@ __device__ __forceinline__ int dfs_reach_wave(const G &g, int i0, int top, int *
             head--;
             if (head < 0) break;
             if (head < lo) { // the stack has unwound past the ring: refill 64 levels
+                WAVE_LOCKSTEP(); // (slot `head` may still hold level head + DFS_RING, which every lane has read by now)
                 const int h = head - lane;
                 if (h >= 0) {
                     R->i[h & (DFS_RING - 1)] = xi[h];

@@ -378,6 +378,7 @@ __device__ __forceinline__ void sweep_scatter(const Cols &C, int k0, int dir, in
         const bool has_b = s + 1 < n;
         const int wb = widx(kb, Pb);
         double ownb = has_b ? x[wb] : 0.0; // before this step's scatter is issued
+        WAVE_LOCKSTEP();                   // (every lane has its own entry before any lane scatters into it)
         C.diag(Pc);
         const ColEnt Ec = C.ent(Pc, 0);
         const ColPtr Pd = C.ptr(k + 3 * dir);

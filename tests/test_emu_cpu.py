@@ -4,7 +4,9 @@ one-wave-per-matrix kernel (k_pivot_loop_wave) and with the general pivot paths,
 the oracle -- canonical factors, counters and the number of pivots per pivot routine, bit for bit.
 
 This is a DIAGNOSTIC build: the product path (libblu_hip.so) never loads it and has no CPU fallback.  It is what lets
-the wave-level kernel logic be checked in the CPU suite (and run under AddressSanitizer: `make emu_asan`).
+the wave-level kernel logic be checked in the CPU suite (and run under AddressSanitizer: `make emu_asan`).  The solves,
+the sweeps of the statistics and the update path are in tests/test_emu_cpu_solves.py; the chain pipeline of a single
+factorize (k_chain.hip) is not validated under the emulator.
 Each case runs in a child process: the library path is fixed when blu_amd is first imported."""
 import os
 import subprocess
@@ -167,9 +169,8 @@ def test_norms_of_rows_of_every_length_on_the_cpu(emu_lib, batch):
     bases on which summing that row in storage order instead of the pivot order of its columns changes INFNORM): the
     short-row paths and the long-row pass of k_stats.hip, as a batch (k_stats + k_stats_tail<512>) and one basis at a
     time (k_stats with the tail; BLU_PIVOT_KERNEL=1, as the default single-basis pivot kernel is not emulated).
-    Only NORM_L, NORM_U, ONENORM and INFNORM are compared: the triangular sweeps of k_stats (condest, residual_test) and
-    solve_dense are not validated under the emulator, so the condition estimates, the residual and
-    the solves are left to the GPU suite (tests/test_gpu_stats_rows.py)."""
+    NORM_L, NORM_U, ONENORM and INFNORM are compared here; the condition estimates, RESIDUAL_TEST and the solves -- the
+    triangular sweeps of k_stats and solve_dense -- are compared with the oracle in tests/test_emu_cpu_solves.py."""
     code = CHILD_STATS % {"root": ROOT, "m": 600, "rowlens": [17, 33, 257, 590], "batch": batch}
     env = dict(os.environ, BLU_HIP_LIB=emu_lib, BLU_PIVOT_KERNEL="0" if batch else "1")
     out = subprocess.run([sys.executable, "-c", code], env=env, capture_output=True, text=True, timeout=600)
@@ -184,8 +185,8 @@ from blu_amd import keys as K
 from oracle import orc
 from tests import util
 assert b"gfx950" in blu_amd.lib().blu_hip_version()
-# what the emulator validates of a factorize that succeeded: the counters, the pivots, the matrix
-# norms and what derives from them; after a refused factorize every getter is compared
+# what this test compares of a factorize that succeeded: the counters, the pivots, the matrix norms and what derives from
+# them (the other statistics: tests/test_emu_cpu_solves.py); after a refused factorize every getter is compared
 EMU_STATS = ("M", "NUPDATE", "NFACTORIZE", "L_NZ", "U_NZ", "MIN_PIVOT", "MAX_PIVOT", "NORM_L", "NORM_U", "ONENORM", "INFNORM",
              "MATRIX_NZ", "RANK", "BUMP_SIZE", "BUMP_NZ", "NSEARCH_PIVOT", "FACTOR_FLOPS", "UPDATE_COST_DENOM", "RANKDEF",
              "L_FLOPS", "U_FLOPS", "NFORREST", "R_NZ", "UPDATE_COST")

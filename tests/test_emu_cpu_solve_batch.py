@@ -2,10 +2,9 @@
 tests/test_emu_cpu.py) runs the host side of the batch solve on small bases -- per-member statuses of a mixed call,
 refusals of the whole call, and handles that stay usable afterwards.
 
-The triangular sweeps rely on wave lockstep the emulator does not reproduce: under it the
-solutions of blu_hip_solve_dense and of the batch are not the oracle's, so their bits are left to
-tests/test_gpu_solve_batch.py.  The update path (solve_for_update / update) does not run under the emulator either, so
-members with an updated factorization are covered on the GPU only.  Each case runs in a child process: the library
+The solutions of the batch and of blu_hip_solve_dense on the same handles are compared with the oracle's bit for bit
+(the sweeps of k_sweep.h run in lockstep under the emulator where they rely on it: DESIGN.md section 4b); members with an
+updated factorization are in tests/test_emu_cpu_solves.py.  Each case runs in a child process: the library
 path is fixed when blu_amd is first imported."""
 import os
 import subprocess
@@ -29,11 +28,15 @@ specs = [(200, 8, 8, 0.5, 1, 0.3), (150, 5, 4, 0.8, 3, 0.6), (180, 6, 6, 0.5, 4,
 mats = [orc.gen_lp_basis(*s) for s in specs]
 
 
-def oracle_factors(cp, ri, v):
+def oracle_of(cp, ri, v):
     o = orc.OracleBLU(len(cp) - 1, 64 * len(ri) + 1024)
     o.set_fix_d3(True)
     assert o.factorize(cp[:-1], cp[1:], ri, v) == K.OK
-    return o.get_factors()
+    return o
+
+
+def oracle_factors(cp, ri, v):
+    return oracle_of(cp, ri, v).get_factors()
 
 
 def same_factors(h, cp, ri, v):
@@ -61,12 +64,15 @@ n = len(hs)
 want = [K.OK, K.OK, K.OK, K.OK, K.ERROR_INVALID_CALL, K.OK, K.ERROR_INVALID_CALL]
 rng = np.random.default_rng(5)
 rhs = [rng.standard_normal(h.m) for h in hs]
+oracles = {0: oracle_of(*mats[0]), 1: oracle_of(*mats[1]), 2: oracle_of(*mats[2]), 3: oracle_of(*mats[0])}
 for tr in "NTnt":
     sols, st = blu_amd.solve_dense_batch(hs, rhs, tr)
     assert st == want, (tr, st)
     assert [len(x) for x in sols] == [h.m for h in hs]
     assert not sols[4].any() and not sols[6].any()                   # members that were not solved: untouched
     assert all(np.isfinite(x).all() for x in sols)
+    for k, o in oracles.items():                                     # the members that were solved: the oracle's bits
+        assert np.array_equal(sols[k], o.solve_dense(rhs[k], tr.upper())), (tr, k)
 
 # the C entry itself: return value and statuses
 L.blu_hip_solve_dense_batch.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_char, C.c_int, C.c_void_p]
@@ -125,6 +131,8 @@ for k, (h, w) in enumerate(zip(hs, want)):
             assert e.status == w == K.ERROR_INVALID_CALL, (k, e.status)
         else:
             assert w == K.OK and len(x) == h.m, k
+            if k in oracles:
+                assert np.array_equal(x, oracles[k].solve_dense(rhs[k], tr)), (k, tr)
 for h, (cp, ri, v) in zip(hb, mats):
     assert h.factorize(cp[:-1], cp[1:], ri, v) == K.OK
     same_factors(h, cp, ri, v)
@@ -132,6 +140,8 @@ assert hbad.factorize(cp1[:-1], cp1[1:], ri1, v1) == K.OK
 same_factors(hbad, cp1, ri1, v1)
 sols, st = blu_amd.solve_dense_batch(hb + [hbad], rhs[:3] + [rhs[6]], "N")
 assert st == [K.OK] * 4, st
+for x, r, mat in zip(sols, rhs[:3] + [rhs[6]], mats + [mats[1]]):
+    assert np.array_equal(x, oracle_of(*mat).solve_dense(r, "N"))
 print("EMU SOLVE BATCH OK")
 """
 
@@ -145,7 +155,8 @@ def emu_lib():
 
 def test_solve_dense_batch_statuses_refusals_and_reuse_on_the_cpu(emu_lib):
     """a mixed call (fresh from factorize_batch and from factorize, never factorized, m = 0, last factorize refused):
-    per-member statuses and return values of the C entry, the refusals of the whole call, handles usable afterwards"""
+    per-member statuses and return values of the C entry, the refusals of the whole call, handles usable afterwards;
+    every solution, of the batch and of the single solves, equal to the oracle's bit for bit"""
     env = dict(os.environ, BLU_HIP_LIB=emu_lib, BLU_PIVOT_KERNEL="1")
     out = subprocess.run([sys.executable, "-c", CHILD % {"root": ROOT}], env=env, capture_output=True, text=True, timeout=900)
     assert out.returncode == 0, out.stdout[-2000:] + out.stderr[-4000:]

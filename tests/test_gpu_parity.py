@@ -680,6 +680,27 @@ def test_solve_sparse_golden_fixtures(blu):
             assert np.array_equal(il, g[key + "_ilhs"]) and np.array_equal(h.lhs[il], g[key + "_xlhs"]), key
 
 
+@pytest.mark.parametrize("thres", [0.05, 1.0])
+def test_solve_sparse_dfs_deeper_than_the_lds_ring(blu, oracle, thres):
+    """B = I + superdiagonal of ones, m = 5000: the reach of e_{m-1} ('N') and of e_0 ('T') is one chain of m nodes, so the depth-first search of k_solve_sparse.hip stacks m levels -- its LDS ring (DFS_RING = 2048) wraps
+    twice on the way down and is refilled from global memory, 64 levels at a time, on the way back.  All values are 1,
+    nothing falls below droptol: nzlhs == m.  Pattern order, values and flop counters equal the oracle's, with the
+    second triangular solve on the symbolic branch (SPARSE_THRES 1.0) and, where nz > 0.05 m, on the sequential one."""
+    m = 5000
+    cp = np.concatenate(([0], np.arange(1, 2 * m, 2))).astype(np.uint64)
+    ri = np.concatenate([[j - 1, j] if j else [0] for j in range(m)]).astype(np.uint64)
+    v = np.ones(len(ri))
+    g, o, sg, so = _both(blu, oracle, cp, ri, v, params={K.PARAM_SPARSE_THRES: thres})
+    assert sg == so == K.OK
+    for trans, i in (("N", m - 1), ("T", 0)):
+        st_o, il_o, lhs_o = o.solve_sparse([i], [1.0], trans)
+        assert g.solve_sparse([i], [1.0], trans) == st_o == K.OK
+        assert g.nzlhs == len(il_o) == m, (trans, g.nzlhs, len(il_o))
+        assert np.array_equal(g.ilhs[:g.nzlhs], il_o), trans
+        assert np.array_equal(g.lhs, lhs_o), (trans, np.abs(g.lhs - lhs_o).max())
+        assert g.stat(K.STAT_L_FLOPS) == o.stat(K.STAT_L_FLOPS) and g.stat(K.STAT_U_FLOPS) == o.stat(K.STAT_U_FLOPS), trans
+
+
 @pytest.mark.parametrize("spec", [(300, 5, 4, 0.5, 1, 0.3), (2000, 8, 8, 0.5, 1, 0.3), (1500, 8, 16, 0.2, 3, 1.0), (6000, 8, 8, 0.5, 1, 0.3)],
                          ids=lambda s: "m%d" % s[0])
 def test_solve_dense_identical_to_oracle(blu, oracle, spec):

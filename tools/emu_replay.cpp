@@ -1,0 +1,203 @@
+// emu_replay.cpp -- replays a tape of C-ABI calls (include/blu_hip.h) against the library it is linked with and compares
+// every result, bit for bit, with the one recorded on the tape.  Built by `make emu_replay` (against libblu_emu.so) and
+// `make emu_replay_asan` (against libblu_emu_asan.so, itself compiled with -fsanitize=address, so the executable carries
+// the sanitizer runtime and the kernels of the CPU emulation build run under AddressSanitizer without any preloading).
+// tests/test_emu_cpu_solves.py writes the tape from the CPU oracle.
+//
+//   emu_replay TAPE          exit status 0: every call gave the recorded result; 1: first difference (named on stderr);
+//                            2: unreadable tape
+//
+// Tape: 8-byte words in host byte order (int64, or the bits of a double).  word 0 = TAPE_MAGIC, then records
+//   OP_NEW      m b_nz                                      a new handle (the previous one is freed)
+//   OP_EXTRA    n                                           blu_hip_dbg_set_upd_extra(n): arena slack of the update path
+//   OP_PARAM    key value(double) status
+//   OP_FACT     nnz begin[m] end[m] b_i[nnz] b_x[nnz] status
+//   OP_DENSE    trans rhs[m] status lhs[m]
+//   OP_SPARSE   trans nzrhs irhs[nzrhs] xrhs[nzrhs] status nzlhs ilhs[nzlhs] lhs[m]      (nzlhs.. only if status == 0)
+//   OP_FORUPD   trans nzrhs irhs[nzrhs] has_x xrhs[nzrhs if has_x] want status [nzlhs ilhs[nzlhs] lhs[m] if want and status == 0]
+//   OP_UPDATE   xtbl(double) status
+//   OP_STAT     key value(double)
+//   OP_END
+#include "../include/blu_hip.h"
+
+#include <cstdio>
+#include <cstdlib>
+#include <cstring>
+#include <vector>
+
+// the one debug hook of the library the update tapes need (blu_update.inc); not part of the product ABI
+extern "C" int blu_hip_dbg_set_upd_extra(blu_hip *h, int64_t extra);
+
+enum { OP_END = 0, OP_NEW, OP_EXTRA, OP_PARAM, OP_FACT, OP_DENSE, OP_SPARSE, OP_FORUPD, OP_UPDATE, OP_STAT };
+static const int64_t TAPE_MAGIC = 0x3145504154554c42LL; // "BLUTAPE1"
+static const char *const OP_NAME[] = {"end", "new", "dbg_set_upd_extra", "set_param", "factorize", "solve_dense", "solve_sparse",
+                                      "solve_for_update", "update", "get_stat"};
+
+static std::vector<int64_t> tape;
+static size_t pos = 0;
+static long ncall = 0;
+static int64_t op = 0;
+
+static const int64_t *take(size_t n)
+{
+    if (n > tape.size() - pos) {
+        fprintf(stderr, "emu_replay: tape ends inside call %ld (%s)\n", ncall, OP_NAME[op]);
+        exit(2);
+    }
+    const int64_t *p = tape.data() + pos;
+    pos += n;
+    return p;
+}
+static int64_t word() { return *take(1); }
+static double real()
+{
+    double x;
+    memcpy(&x, take(1), 8);
+    return x;
+}
+static void differ(const char *what, long k, const void *got, const void *want, bool is_double)
+{
+    fprintf(stderr, "emu_replay: call %ld (%s): %s", ncall, OP_NAME[op], what);
+    if (k >= 0) fprintf(stderr, "[%ld]", k);
+    if (is_double) {
+        double g, w;
+        memcpy(&g, got, 8);
+        memcpy(&w, want, 8);
+        fprintf(stderr, " is %.17g, the tape has %.17g\n", g, w);
+    } else {
+        int64_t g, w;
+        memcpy(&g, got, 8);
+        memcpy(&w, want, 8);
+        fprintf(stderr, " is %lld, the tape has %lld\n", (long long)g, (long long)w);
+    }
+    exit(1);
+}
+static void same_int(const char *what, int64_t got, int64_t want)
+{
+    if (got != want) differ(what, -1, &got, &want, false);
+}
+static void same_words(const char *what, const void *got, const int64_t *want, size_t n, bool is_double)
+{
+    const char *g = (const char *)got;
+    for (size_t k = 0; k < n; k++)
+        if (memcmp(g + 8 * k, want + k, 8) != 0) differ(what, (long)k, g + 8 * k, want + k, is_double);
+}
+// status, and for a solve that succeeded nzlhs, the pattern in order and the bits of the dense solution
+static void same_solution(int status, int64_t m, int64_t nzlhs, const std::vector<int64_t> &ilhs, const std::vector<double> &lhs, bool want)
+{
+    same_int("status", status, word());
+    if (status != BLU_OK || !want) return;
+    same_int("nzlhs", nzlhs, word());
+    same_words("ilhs", ilhs.data(), take((size_t)nzlhs), (size_t)nzlhs, false);
+    same_words("lhs", lhs.data(), take((size_t)m), (size_t)m, true);
+}
+
+int main(int argc, char **argv)
+{
+    if (argc != 2) {
+        fprintf(stderr, "usage: emu_replay TAPE\n");
+        return 2;
+    }
+    FILE *f = fopen(argv[1], "rb");
+    if (!f) {
+        perror(argv[1]);
+        return 2;
+    }
+    int64_t buf[4096];
+    size_t n;
+    while ((n = fread(buf, 8, 4096, f)) > 0) tape.insert(tape.end(), buf, buf + n);
+    fclose(f);
+    if (tape.empty() || tape[0] != TAPE_MAGIC) {
+        fprintf(stderr, "emu_replay: %s is not a tape\n", argv[1]);
+        return 2;
+    }
+    pos = 1;
+    blu_hip *h = nullptr;
+    int64_t m = 0;
+    for (;;) {
+        op = word();
+        if (op < OP_END || op > OP_STAT) {
+            fprintf(stderr, "emu_replay: unknown record %lld after call %ld\n", (long long)op, ncall);
+            return 2;
+        }
+        if (op == OP_END) break;
+        ncall++;
+        if (op != OP_NEW && !h) {
+            fprintf(stderr, "emu_replay: call %ld (%s) before a handle exists\n", ncall, OP_NAME[op]);
+            return 2;
+        }
+        switch (op) {
+        case OP_NEW: {
+            if (h) blu_hip_free(h);
+            m = word();
+            const int64_t b_nz = word();
+            h = blu_hip_new(m, b_nz, 0);
+            same_int("handle", h != nullptr, 1);
+            break;
+        }
+        case OP_EXTRA:
+            same_int("status", blu_hip_dbg_set_upd_extra(h, word()), BLU_OK);
+            break;
+        case OP_PARAM: {
+            const int key = (int)word();
+            const double value = real();
+            same_int("status", blu_hip_set_param(h, key, value), word());
+            break;
+        }
+        case OP_FACT: {
+            const size_t nnz = (size_t)word();
+            const uint64_t *bb = (const uint64_t *)take((size_t)m), *be = (const uint64_t *)take((size_t)m);
+            const uint64_t *bi = (const uint64_t *)take(nnz);
+            const double *bx = (const double *)take(nnz);
+            same_int("status", blu_hip_factorize(h, bb, be, bi, bx, nnz), word());
+            break;
+        }
+        case OP_DENSE: {
+            const char trans = (char)word();
+            const double *rhs = (const double *)take((size_t)m);
+            std::vector<double> lhs((size_t)m, 0.0);
+            const int st = blu_hip_solve_dense(h, rhs, lhs.data(), trans);
+            same_int("status", st, word());
+            if (st == BLU_OK) same_words("lhs", lhs.data(), take((size_t)m), (size_t)m, true);
+            break;
+        }
+        case OP_SPARSE:
+        case OP_FORUPD: {
+            const char trans = (char)word();
+            const int64_t nzrhs = word();
+            const uint64_t *irhs = (const uint64_t *)take((size_t)nzrhs);
+            const bool has_x = op == OP_SPARSE || word() != 0;
+            const double *xrhs = has_x ? (const double *)take((size_t)nzrhs) : nullptr;
+            const bool want = op == OP_SPARSE || word() != 0;
+            std::vector<int64_t> ilhs((size_t)m, 0); // (exactly m: an entry written behind them is an AddressSanitizer report)
+            std::vector<double> lhs((size_t)m, 0.0);
+            int64_t nzlhs = 0;
+            int st;
+            if (op == OP_SPARSE)
+                st = blu_hip_solve_sparse(h, nzrhs, irhs, xrhs, &nzlhs, ilhs.data(), lhs.data(), trans);
+            else if (want)
+                st = blu_hip_solve_for_update(h, nzrhs, irhs, xrhs, &nzlhs, ilhs.data(), lhs.data(), trans);
+            else
+                st = blu_hip_solve_for_update(h, nzrhs, irhs, xrhs, nullptr, nullptr, nullptr, trans);
+            same_solution(st, m, nzlhs, ilhs, lhs, want);
+            break;
+        }
+        case OP_UPDATE: {
+            const double xtbl = real();
+            same_int("status", blu_hip_update(h, xtbl), word());
+            break;
+        }
+        case OP_STAT: {
+            const int key = (int)word();
+            const double got = blu_hip_get_stat(h, key);
+            char what[32];
+            snprintf(what, sizeof what, "statistic %d", key);
+            same_words(what, &got, take(1), 1, true);
+            break;
+        }
+        }
+    }
+    if (h) blu_hip_free(h);
+    printf("REPLAY OK: %ld calls\n", ncall);
+    return 0;
+}

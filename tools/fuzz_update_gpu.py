@@ -4,10 +4,11 @@ STEP with its CPU twin (oracle/orc_update.c, the intended algorithm: not referen
 pattern (order included) and value, ten counters after every update must be identical; every solve is also checked by its
 backward error against the modified matrix held in scipy (tests/util_update.py).
 
-   python tools/fuzz_update_gpu.py [--seed S] [--start A] [--count N] [--log FILE]      (needs a GPU)
+   python tools/fuzz_update_gpu.py [--seed S] [--start A] [--count N] [--log FILE]
+       (on a GPU; or, slowly, on the CPU emulation build: BLU_HIP_LIB=.../libblu_emu.so BLU_PIVOT_KERNEL=1 BLU_HIP_NO_CHAIN=1)
 
 Case n of seed S is the same whichever slice it is run in (one child generator per case).  tests/test_gpu_fuzz.py runs
-slices in fresh child processes."""
+slices in fresh child processes, tests/test_emu_cpu_solves.py a short one under the emulation build."""
 import argparse
 import os
 import sys
