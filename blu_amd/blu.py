@@ -10,6 +10,8 @@ with the same method names, argument meaning and error behaviour:
     .get_factors()                                 BLU::get_factors         blu.rs:139
     .solve_dense(rhs, trans)                       BLU::solve_dense         blu.rs:182
     solve_dense_batch(handles, rhs, trans)         solve_dense for many handles in one call (batch extension)
+    solve_for_update_batch(handles, irhs, xrhs)    solve_for_update for many handles in one call (batch extension)
+    update_batch(handles, xtbl)                    update for many handles in one call (batch extension)
     .set_param / .stat                             pub fields / getters     lu.rs:11-66, 398-684
 
 There is NO CPU fallback: if the shared library is missing, or no gfx950 device is visible, this
@@ -38,7 +40,7 @@ EXPORTS = [
     "blu_hip_factorize", "blu_hip_factorize_device", "blu_hip_get_factors", "blu_hip_solve_dense",
     "blu_hip_factorize_batch", "blu_hip_version", "blu_hip_device_count", "blu_hip_last_error",
     "blu_hip_solve_sparse", "blu_hip_solve_for_update", "blu_hip_update", "blu_hip_set_skip_stats", "blu_hip_gen_lp_basis",
-    "blu_hip_solve_dense_batch",
+    "blu_hip_solve_dense_batch", "blu_hip_solve_for_update_batch", "blu_hip_update_batch",
 ]
 
 
@@ -217,11 +219,80 @@ def solve_dense_batch(handles, rhs=None, trans="N", device_ptrs=None):
     return out if sols is None else (sols, out)
 
 
+def _refused(rc, handles, what):
+    """A refusal of a whole update-batch call raises; ERROR_INVALID_ARGUMENT is also a member's status (an index out of
+    range), so it counts as a refusal only for what the call refuses with it: a handle twice, or two devices."""
+    if rc == K.ERROR_ARGUMENT_MISSING or (rc == K.ERROR_INVALID_ARGUMENT and (
+            len({h._h for h in handles}) != len(handles) or len({h.device for h in handles}) > 1)):
+        raise BluError(rc, what + " refused")
+
+
+def solve_for_update_batch(handles, irhs, xrhs=None, trans="N", want_solution=True):
+    """BLU.solve_for_update for len(handles) handles of one device in one call (one wave per member; per member the
+    status, pattern, values and statistics of the single call, bit for bit).
+
+    irhs[k] / xrhs[k]: member k's arguments as BLU.solve_for_update takes them; trans applies to every member (xrhs may be
+    None for 'T').  With want_solution each handle's previous solution is cleared and the new one left in h.lhs /
+    h.ilhs[0..h.nzlhs), as BLU.solve_for_update does.  Returns the per-member statuses.  A refused call raises BluError, as
+    does ERROR_DEVICE or ERROR_OUT_OF_MEMORY of a member; the other codes are only reported in the member's status."""
+    n = len(handles)
+    if len(irhs) != n or (xrhs is not None and len(xrhs) != n):
+        raise ValueError("solve_for_update_batch: one right-hand side per handle")
+    L = lib()
+    L.blu_hip_solve_for_update_batch.argtypes = [C.c_void_p, C.c_int] + [C.c_void_p] * 6 + [C.c_char, C.c_void_p]
+    N = max(n, 1)
+    hs = (C.c_void_p * N)(*[h._h for h in handles])
+    irs = [np.ascontiguousarray(a, dtype=np.uint64) for a in irhs]
+    xrs = None if xrhs is None else [np.ascontiguousarray(a, dtype=np.float64) for a in xrhs]
+    nzr = (C.c_int64 * N)(*[len(a) for a in irs])
+    pi, px, pil, pl = (C.c_void_p * N)(), (C.c_void_p * N)(), (C.c_void_p * N)(), (C.c_void_p * N)()
+    for k, h in enumerate(handles):
+        h._clear_lhs()
+        pi[k] = irs[k].ctypes.data or 8  # (an empty column: any non-NULL pointer)
+        if xrs is not None:
+            px[k] = xrs[k].ctypes.data or 8
+        pil[k], pl[k] = h.ilhs.ctypes.data, h.lhs.ctypes.data
+    nzl = (C.c_int64 * N)()
+    st = (C.c_int * N)()
+    rc = L.blu_hip_solve_for_update_batch(hs, n, nzr, pi, None if xrs is None else px, nzl if want_solution else None,
+                                          pil if want_solution else None, pl if want_solution else None, trans.encode()[0:1], st)
+    _refused(rc, handles, "solve_for_update_batch")
+    out = [int(s) for s in st][:n]
+    for k, (h, s) in enumerate(zip(handles, out)):
+        if s in (K.ERROR_DEVICE, K.ERROR_OUT_OF_MEMORY):
+            raise BluError(s, h.last_error())
+        if s == K.OK and want_solution:
+            h.nzlhs = int(nzl[k])
+    return out
+
+
+def update_batch(handles, xtbl):
+    """BLU.update for len(handles) handles of one device in one call: xtbl[k] for handles[k].  Returns the per-member
+    statuses; errors are raised as by solve_for_update_batch."""
+    n = len(handles)
+    if len(xtbl) != n:
+        raise ValueError("update_batch: one xtbl per handle")
+    L = lib()
+    L.blu_hip_update_batch.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p]
+    N = max(n, 1)
+    hs = (C.c_void_p * N)(*[h._h for h in handles])
+    xt = (C.c_double * N)(*[float(x) for x in xtbl])
+    st = (C.c_int * N)()
+    rc = L.blu_hip_update_batch(hs, n, xt, st)
+    _refused(rc, handles, "update_batch")
+    out = [int(s) for s in st][:n]
+    for h, s in zip(handles, out):
+        if s in (K.ERROR_DEVICE, K.ERROR_OUT_OF_MEMORY):
+            raise BluError(s, h.last_error())
+    return out
+
+
 class BLU:
     """`struct BLU` (src/blu.rs:9-20) backed by the HIP implementation."""
 
     def __init__(self, m, b_nz, device=0):
         self.m = int(m)
+        self.device = int(device)
         self.lhs = self.ilhs = None  # BLU.lhs / BLU.ilhs / BLU.nzlhs (blu.rs:12-17): solve_sparse results
         self.nzlhs = 0
         self._h = lib().blu_hip_new(int(m), int(b_nz), int(device))

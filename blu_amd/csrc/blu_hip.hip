@@ -764,7 +764,7 @@ static int ensure_sparse_ws(blu_hip *h)
     SparseWs &W = h->sw;
     bool a = dalloc(h, &W.marked, M) && dalloc(h, &W.psym, M) && dalloc(h, &W.pat, M) && dalloc(h, &W.pstack, M) && dalloc(h, &W.estack, M) &&
              dalloc(h, &W.work, M) && dalloc(h, &W.xlhs, M) && dalloc(h, &W.ilhs, M) && dalloc(h, &W.xval, M) &&
-             dalloc(h, &W.out, 4) && (W.lt_ptr || dalloc(h, &W.lt_ptr, M + 1)) && (W.lt_cur || dalloc(h, &W.lt_cur, M));
+             dalloc(h, &W.out, 5) && (W.lt_ptr || dalloc(h, &W.lt_ptr, M + 1)) && (W.lt_cur || dalloc(h, &W.lt_cur, M));
     a = a && hip_ok(h, hipMemset(W.marked, 0, M * sizeof(int)), "hipMemset") &&
         hip_ok(h, hipMemset(W.work, 0, M * sizeof(double)), "hipMemset") &&
         hip_ok(h, hipMemset(W.xlhs, 0, M * sizeof(double)), "hipMemset");
@@ -893,6 +893,7 @@ extern "C" int blu_hip_solve_dense(blu_hip *h, const double *rhs, double *lhs, c
 }
 
 #include "blu_solve_batch.inc"
+#include "blu_update_batch.inc"
 
 // solve_sparse -- src/solve_sparse.rs:36-68, lu/solve_sparse.rs:11-360 (fresh factorization: nforrest == 0)
 extern "C" int blu_hip_solve_sparse(blu_hip *h, int64_t nzrhs, const uint64_t *irhs, const double *xrhs, int64_t *p_nzlhs,

@@ -22,12 +22,9 @@ static bool download_upd(blu_hip *h)
     return hip_ok(h, hipMemcpy(&h->ust, h->uw.st, sizeof(UpdState), hipMemcpyDeviceToHost), "d2h update state");
 }
 
-// the mutable copies of U, the maps, the pivot sequence and the eta file of THIS factorization
-static int ensure_upd(blu_hip *h)
+// room for the mutable copies of U, the maps, the pivot sequence and the eta file of THIS factorization
+static int ensure_upd_ws(blu_hip *h)
 {
-    int st = ensure_lt(h); // sparse workspace + row-wise L
-    if (st != BLU_OK) return st;
-    if (h->upd_for_nfact == h->nfactorize) return BLU_OK;
     UpdWs &U = h->uw;
     const size_t M = (size_t)h->m;
     if (h->upd_alloc_m != h->m) {
@@ -62,6 +59,18 @@ static int ensure_upd(blu_hip *h)
         if (!dalloc(h, &U.ridx, (size_t)rneed) || !dalloc(h, &U.rval, (size_t)rneed)) return BLU_ERROR_OUT_OF_MEMORY;
         U.rcapacity = (int)rneed;
     }
+    return BLU_OK;
+}
+
+// the mutable copies of U, the maps, the pivot sequence and the eta file of THIS factorization
+static int ensure_upd(blu_hip *h)
+{
+    int st = ensure_lt(h); // sparse workspace + row-wise L
+    if (st != BLU_OK) return st;
+    if (h->upd_for_nfact == h->nfactorize) return BLU_OK;
+    st = ensure_upd_ws(h);
+    if (st != BLU_OK) return st;
+    UpdWs &U = h->uw;
     // the totals count over the life of the handle: LU::reset leaves them (lu.rs:329-359), k_upd_init starts from zero
     const long long nsymperm_total = h->ust.nsymperm_total, nunsymperm_total = h->ust.nunsymperm_total, nforrest_total = h->ust.nforrest_total;
     hipLaunchKernelGGL(k_upd_init, dim3(1), dim3(1024), 0, h->stream, h->dD, h->dO, U);

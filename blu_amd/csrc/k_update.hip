@@ -90,13 +90,11 @@ __device__ __forceinline__ int wave_append(int *pattern, int nz, bool take, int 
 // ---------------------------------------------------------------------------------------------------------
 // k_upd_init: the mutable copies, from the fresh factors (build_factors.rs:283-419 gives the same contents)
 // ---------------------------------------------------------------------------------------------------------
-__global__ void __launch_bounds__(1024) k_upd_init(DevLU *Ds, FinishOut *Os, UpdWs U)
+// (the whole workgroup; sh: 40 ints of LDS for the scan)
+__device__ __forceinline__ void upd_init_block(const DevG &D, const FinishOut &O, const UpdWs &U, int *sh)
 {
-    const DevG D(Ds[0]);
-    const FinishOut &O = Os[0];
     const int tid = threadIdx.x, nt = blockDim.x;
     const int m = D.m, rank = D.s->rank;
-    __shared__ int sh[40];
     UpdState *st = U.st;
     typedef GPTR(const long long) gcll;
     const gcll ucp = (gcll)O.u_colptr, uri = (gcll)O.u_rowidx;
@@ -163,6 +161,11 @@ __global__ void __launch_bounds__(1024) k_upd_init(DevLU *Ds, FinishOut *Os, Upd
         U.rbeg[0] = 0;
     }
 }
+__global__ void __launch_bounds__(1024) k_upd_init(DevLU *Ds, FinishOut *Os, UpdWs U)
+{
+    __shared__ int sh[40];
+    upd_init_block(DevG(Ds[0]), Os[0], U, sh);
+}
 
 // garbage_perm (garbage_perm.rs:16-48): keep the last occurrence of every column in the pivot sequence, order kept.
 // Whole wave, 64 positions at a time from the back: a position is kept if its column has not been seen further back
@@ -222,11 +225,10 @@ __device__ __forceinline__ void garbage_perm_wave(const UpdWs &U, int m, int *ma
 // k_solve_upd: solve_sparse on an updated factorization (mode 0) and solve_for_update (mode 1), both systems.
 // out[0] nz of the solution, [1] l_flops, [2] u_flops, [3] branch (1 sparse, 2 sequential), [4] r_flops
 // ---------------------------------------------------------------------------------------------------------
-__global__ void __launch_bounds__(64) k_solve_upd(DevLU *Ds, SparseWs W, UpdWs U, int mode, int want_solution, int nrhs, const int *irhs,
-                                                  const double *xrhs, int trans, int marker, int nz_sparse)
+__device__ __forceinline__ void solve_upd_wave(const DevG &D, const SparseWs &W, const UpdWs &U, int mode, int want_solution, int nrhs,
+                                               const int *irhs, const double *xrhs, int trans, int marker, int nz_sparse, DfsRing *ring)
 {
-    __shared__ DfsRing dfs_ring;
-    const DevG D(Ds[0]);
+    DfsRing &dfs_ring = *ring;
     const int lane = lane_id();
     const int m = D.m;
     const double droptol = D.droptol;
@@ -496,11 +498,18 @@ __global__ void __launch_bounds__(64) k_solve_upd(DevLU *Ds, SparseWs W, UpdWs U
         W.out[1] = l_flops;
         W.out[2] = u_flops;
         W.out[3] = branch;
+        W.out[4] = r_flops;
         st->l_flops += l_flops;
         st->u_flops += u_flops;
         st->r_flops += r_flops;
         st->update_cost_numer += (double)r_flops;
     }
+}
+__global__ void __launch_bounds__(64) k_solve_upd(DevLU *Ds, SparseWs W, UpdWs U, int mode, int want_solution, int nrhs, const int *irhs,
+                                                  const double *xrhs, int trans, int marker, int nz_sparse)
+{
+    __shared__ DfsRing dfs_ring;
+    solve_upd_wave(DevG(Ds[0]), W, U, mode, want_solution, nrhs, irhs, xrhs, trans, marker, nz_sparse, &dfs_ring);
 }
 
 // ---------------------------------------------------------------------------------------------------------
@@ -632,9 +641,8 @@ __device__ __forceinline__ void permute_lane0(const UpdWs &U, const int *jlist, 
     U.qmap[in_] = j0;
 }
 
-__global__ void __launch_bounds__(64) k_update(DevLU *Ds, SparseWs W, UpdWs U, double xtbl, int marker)
+__device__ __forceinline__ void update_wave(const DevG &D, const SparseWs &W, const UpdWs &U, double xtbl, int marker)
 {
-    const DevG D(Ds[0]);
     const int lane = lane_id();
     const int m = D.m;
     UpdState *st = U.st;
@@ -964,6 +972,88 @@ __global__ void __launch_bounds__(64) k_update(DevLU *Ds, SparseWs W, UpdWs U, d
 #endif
     (void)nz_spike;
     (void)s_spike_diag;
+}
+__global__ void __launch_bounds__(64) k_update(DevLU *Ds, SparseWs W, UpdWs U, double xtbl, int marker)
+{
+    update_wave(DevG(Ds[0]), W, U, xtbl, marker);
+}
+
+// ---------------------------------------------------------------------------------------------------------
+// The same three for the members of blu_hip_solve_for_update_batch / blu_hip_update_batch: one workgroup per member,
+// the descriptors of member b in Ds[b] / Os[b] / Ws[b] / Us[b], what the call hands it in Ms[b].  Each wrapper leaves
+// the member's UpdState and the counters of its solve in Rs[b], so that the host reads every member with one copy.
+// ---------------------------------------------------------------------------------------------------------
+struct UpdMember {
+    const int *irhs;    // right-hand side of the member inside the packed staging buffer of the call
+    const double *xrhs;
+    double xtbl;        // k_update_batch
+    long long carry[3]; // k_upd_init_batch: nsymperm_total, nunsymperm_total, nforrest_total count over the life of the handle
+    int nrhs, marker, nz_sparse, want_solution;
+};
+struct UpdResult {
+    UpdState st;
+    long long out[5]; // SparseWs::out of a solve that ended with UPD_OK, [4] = r_flops
+};
+
+__device__ __forceinline__ void upd_result_lane0(const SparseWs &W, const UpdWs &U, UpdResult *R, bool solved)
+{
+    wave_mem_sync();
+    if (lane_id() == 0) {
+        R->st = *U.st;
+        for (int q = 0; q < 5; q++) R->out[q] = solved ? W.out[q] : 0;
+    }
+}
+
+__global__ void __launch_bounds__(1024) k_upd_init_batch(const DevLU *Ds, const FinishOut *Os, const UpdWs *Us, const UpdMember *Ms, UpdResult *Rs)
+{
+    __shared__ int sh[40];
+    const int b = blockIdx.x;
+    const UpdWs U = Us[b];
+    upd_init_block(DevG(Ds[b]), Os[b], U, sh);
+    if (threadIdx.x == 0) { // (the thread that wrote the state)
+        U.st->nsymperm_total = Ms[b].carry[0];
+        U.st->nunsymperm_total = Ms[b].carry[1];
+        U.st->nforrest_total = Ms[b].carry[2];
+        Rs[b].st = *U.st;
+        for (int q = 0; q < 5; q++) Rs[b].out[q] = 0;
+    }
+}
+
+__global__ void __launch_bounds__(64) k_solve_upd_batch(const DevLU *Ds, const SparseWs *Ws, const UpdWs *Us, const UpdMember *Ms, UpdResult *Rs,
+                                                        int trans)
+{
+    __shared__ DfsRing dfs_ring;
+    const int b = blockIdx.x;
+    const UpdMember M = Ms[b];
+    const SparseWs W = Ws[b];
+    const UpdWs U = Us[b];
+    solve_upd_wave(DevG(Ds[b]), W, U, 1, M.want_solution, M.nrhs, M.irhs, M.xrhs, trans, M.marker, M.nz_sparse, &dfs_ring);
+    upd_result_lane0(W, U, &Rs[b], true);
+}
+
+__global__ void __launch_bounds__(64) k_update_batch(const DevLU *Ds, const SparseWs *Ws, const UpdWs *Us, const UpdMember *Ms, UpdResult *Rs)
+{
+    const int b = blockIdx.x;
+    const UpdMember M = Ms[b];
+    const SparseWs W = Ws[b];
+    const UpdWs U = Us[b];
+    update_wave(DevG(Ds[b]), W, U, M.xtbl, M.marker);
+    upd_result_lane0(W, U, &Rs[b], false);
+}
+
+// the compressed solutions of the members into one buffer: member b's nz = off[b + 1] - off[b] entries of Ws[b].ilhs /
+// Ws[b].xval go to gidx / gval at off[b] (the host computes off from the downloaded counters)
+__global__ void __launch_bounds__(256) k_gather_lhs_batch(const SparseWs *Ws, const long long *off, int *gidx, double *gval)
+{
+    const int b = blockIdx.x;
+    const long long o = off[b];
+    const int nz = (int)(off[b + 1] - o);
+    const int *il = Ws[b].ilhs;
+    const double *xv = Ws[b].xval;
+    for (int n = threadIdx.x; n < nz; n += blockDim.x) {
+        gidx[o + n] = il[n];
+        gval[o + n] = xv[n];
+    }
 }
 
 // ---------------------------------------------------------------------------------------------------------

@@ -222,6 +222,27 @@ int blu_hip_factorize_batch(blu_hip **h, int n,
 int blu_hip_solve_dense_batch(blu_hip **h, int n, const double *const *rhs, double *const *lhs, char trans,
                               int inputs_on_device, int *status);
 
+/* Batch extension: blu_hip_solve_for_update and blu_hip_update for n handles on one device in one call.  Member k gets
+ * exactly what blu_hip_solve_for_update(h[k], nzrhs[k], irhs[k], xrhs[k], &nzlhs[k], ilhs[k], lhs[k], trans) /
+ * blu_hip_update(h[k], xtbl[k]) gives: status, pattern in the same order, the bits of the values, every statistic and
+ * the handle's later behaviour.  trans applies to every member; for a transposed call nzrhs and xrhs may be NULL and
+ * only irhs[k][0] is read.  If nzlhs, ilhs and lhs are all NULL only the updates are prepared; if they are given, a
+ * member whose ilhs[k] or lhs[k] is NULL is prepared without a solution (lhs[k] all zero on entry otherwise).
+ * Each member runs on ONE wave, the members in one launch (k_solve_upd_batch / k_update_batch); a round of the call
+ * costs one upload, one launch, one synchronize and one download whatever n is; members whose kernel asks for storage
+ * are grown and launched again alone.  The first call after a factorization builds the row-wise L and the update
+ * workspace of the members that lack them in one launch each (k_build_lt_batch, k_upd_init_batch).
+ * Refused as a whole, every status[k] carrying the code and no handle touched: NULL h, irhs, a NULL handle or irhs[k],
+ * a forward call with nzrhs, xrhs or an xrhs[k] NULL, NULL xtbl, n < 0 (BLU_ERROR_ARGUMENT_MISSING); the same handle
+ * twice or handles on different devices (BLU_ERROR_INVALID_ARGUMENT).  n == 0 returns BLU_OK.  Everything else is per
+ * member with the code of the single entry (BLU_ERROR_INVALID_CALL, BLU_ERROR_INVALID_ARGUMENT,
+ * BLU_ERROR_MAXIMUM_UPDATES, BLU_ERROR_SINGULAR_UPDATE, BLU_ERROR_OUT_OF_MEMORY, BLU_ERROR_DEVICE) and the other
+ * members run regardless.  status may be NULL.  Returns the most negative member status, else the largest. */
+int blu_hip_solve_for_update_batch(blu_hip **h, int n, const int64_t *nzrhs, const uint64_t *const *irhs,
+                                   const double *const *xrhs, int64_t *nzlhs, int64_t *const *ilhs, double *const *lhs,
+                                   char trans, int *status);
+int blu_hip_update_batch(blu_hip **h, int n, const double *xtbl, int *status);
+
 /* factorize() ends with the statistics tail of src/factorize.rs:121-147 (condest(L), condest(U),
  * residual_test; getters BLU_STAT_CONDEST_* .. BLU_STAT_RESIDUAL_TEST).  It is a chain of 8 triangular
  * sweeps (~17 % of the factorize time at 100k); a caller that never reads those getters can switch

@@ -67,6 +67,11 @@ extern "C" {
         h: *mut BluHip, nzrhs: i64, irhs: *const u64, xrhs: *const f64, p_nzlhs: *mut i64, ilhs: *mut i64, lhs: *mut f64, trans: c_char,
     ) -> c_int;
     fn blu_hip_update(h: *mut BluHip, xtbl: c_double) -> c_int;
+    fn blu_hip_solve_for_update_batch(
+        h: *mut *mut BluHip, n: c_int, nzrhs: *const i64, irhs: *const *const u64, xrhs: *const *const f64, nzlhs: *mut i64,
+        ilhs: *const *mut i64, lhs: *const *mut f64, trans: c_char, status: *mut c_int,
+    ) -> c_int;
+    fn blu_hip_update_batch(h: *mut *mut BluHip, n: c_int, xtbl: *const c_double, status: *mut c_int) -> c_int;
     fn blu_hip_last_error(h: *const BluHip) -> *const c_char;
 }
 
@@ -221,6 +226,7 @@ pub struct BLU {
     /// `pub lu: LU` (`blu.rs:10`).
     pub lu: LU,
     m: usize,
+    device: i32,
     /// Solution of the last `solve_sparse` / `solve_for_update` (dense, `m` entries; `blu.rs:12`).
     pub lhs: Vec<f64>,
     /// Its pattern in the reference's order (`blu.rs:14`).
@@ -246,7 +252,7 @@ impl BLU {
         if h.is_null() {
             return None;
         }
-        Some(BLU { lu: LU { h }, m, lhs: vec![0.0; m], ilhs: vec![0; m], nzlhs: 0, realloc_factor: 1.5 })
+        Some(BLU { lu: LU { h }, m, device, lhs: vec![0.0; m], ilhs: vec![0; m], nzlhs: 0, realloc_factor: 1.5 })
     }
 
     // the library grows its device storage itself (the loops of blu.rs:105-115, 277-283, 324-330): it gets the factor
@@ -368,6 +374,75 @@ impl BLU {
         self.push_realloc_factor();
         status_of(unsafe { blu_hip_update(self.lu.h, xtbl) })
     }
+}
+
+/// `BLU::solve_for_update` for many objects of one device in one call (batch extension, no reference counterpart):
+/// member k gets what `blus[k].solve_for_update(irhs[k].len(), irhs[k], xrhs[k], trans, want_solution)` gives, its
+/// solution left in `blus[k].lhs` / `ilhs[..nzlhs]`.  `Err` is a refusal of the whole call (the same object twice
+/// cannot be expressed here; objects on two devices, or a forward call without `xrhs`); otherwise one result per member.
+pub fn solve_for_update_batch(
+    blus: &mut [&mut BLU], irhs: &[&[usize]], xrhs: Option<&[&[f64]]>, trans: char, want_solution: LUInt,
+) -> Result<Vec<Result<(), Status>>, Status> {
+    let n = blus.len();
+    let transposed = trans == 't' || trans == 'T';
+    if irhs.len() != n || xrhs.map_or(false, |x| x.len() != n) {
+        return Err(Status::ErrorInvalidArgument);
+    }
+    for k in 0..n {
+        if (transposed && irhs[k].is_empty()) || xrhs.map_or(false, |x| x[k].len() < irhs[k].len()) {
+            return Err(Status::ErrorInvalidArgument);
+        }
+    }
+    for b in blus.iter_mut() {
+        b.clear_lhs();
+        b.push_realloc_factor();
+    }
+    let mut hs: Vec<*mut BluHip> = blus.iter().map(|b| b.lu.h).collect();
+    let nzrhs: Vec<i64> = irhs.iter().map(|x| x.len() as i64).collect();
+    // (an empty column: any non-NULL pointer, nothing is read through it)
+    let ip: Vec<*const u64> = irhs.iter().map(|x| if x.is_empty() { 8 as *const u64 } else { x.as_ptr() as *const u64 }).collect();
+    let xp: Option<Vec<*const f64>> = xrhs.map(|xs| xs.iter().map(|x| if x.is_empty() { 8 as *const f64 } else { x.as_ptr() }).collect());
+    let il: Vec<*mut i64> = blus.iter_mut().map(|b| b.ilhs.as_mut_ptr()).collect();
+    let lp: Vec<*mut f64> = blus.iter_mut().map(|b| b.lhs.as_mut_ptr()).collect();
+    let mut nz = vec![0i64; n];
+    let mut st = vec![0 as c_int; n];
+    let want = want_solution != 0;
+    let code = unsafe {
+        blu_hip_solve_for_update_batch(
+            hs.as_mut_ptr(), n as c_int, nzrhs.as_ptr(), ip.as_ptr(), xp.as_ref().map_or(std::ptr::null(), |v| v.as_ptr()),
+            if want { nz.as_mut_ptr() } else { std::ptr::null_mut() }, if want { il.as_ptr() } else { std::ptr::null() },
+            if want { lp.as_ptr() } else { std::ptr::null() }, trans as c_char, st.as_mut_ptr(),
+        )
+    };
+    // -3 is returned by a refusal alone; -4 is also a member's status (an index out of range): a refusal only for two devices
+    if code == -3 || (code == -4 && blus.iter().any(|b| b.device != blus[0].device)) {
+        return status_of(code).map(|_| Vec::new());
+    }
+    for k in 0..n {
+        if st[k] == 0 && want {
+            blus[k].nzlhs = nz[k] as usize;
+        }
+    }
+    Ok(st.iter().map(|&s| status_of(s)).collect())
+}
+
+/// `BLU::update` for many objects of one device in one call: `xtbl[k]` for `blus[k]`; results as by
+/// `solve_for_update_batch`.
+pub fn update_batch(blus: &mut [&mut BLU], xtbl: &[f64]) -> Result<Vec<Result<(), Status>>, Status> {
+    let n = blus.len();
+    if xtbl.len() != n {
+        return Err(Status::ErrorInvalidArgument);
+    }
+    for b in blus.iter_mut() {
+        b.push_realloc_factor();
+    }
+    let mut hs: Vec<*mut BluHip> = blus.iter().map(|b| b.lu.h).collect();
+    let mut st = vec![0 as c_int; n];
+    let code = unsafe { blu_hip_update_batch(hs.as_mut_ptr(), n as c_int, xtbl.as_ptr(), st.as_mut_ptr()) };
+    if code == -3 || (code == -4 && blus.iter().any(|b| b.device != blus[0].device)) {
+        return status_of(code).map(|_| Vec::new());
+    }
+    Ok(st.iter().map(|&s| status_of(s)).collect())
 }
 
 #[cfg(test)]
