@@ -12,6 +12,7 @@ with the same method names, argument meaning and error behaviour:
     solve_dense_batch(handles, rhs, trans)         solve_dense for many handles in one call (batch extension)
     solve_for_update_batch(handles, irhs, xrhs)    solve_for_update for many handles in one call (batch extension)
     update_batch(handles, xtbl)                    update for many handles in one call (batch extension)
+    solve_sparse_batch(handles, irhs, xrhs)        solve_sparse for many handles in one call (batch extension)
     .set_param / .stat                             pub fields / getters     lu.rs:11-66, 398-684
 
 There is NO CPU fallback: if the shared library is missing, or no gfx950 device is visible, this
@@ -41,6 +42,7 @@ EXPORTS = [
     "blu_hip_factorize_batch", "blu_hip_version", "blu_hip_device_count", "blu_hip_last_error",
     "blu_hip_solve_sparse", "blu_hip_solve_for_update", "blu_hip_update", "blu_hip_set_skip_stats", "blu_hip_gen_lp_basis",
     "blu_hip_solve_dense_batch", "blu_hip_solve_for_update_batch", "blu_hip_update_batch",
+    "blu_hip_solve_sparse_batch",
 ]
 
 
@@ -284,6 +286,45 @@ def update_batch(handles, xtbl):
     for h, s in zip(handles, out):
         if s in (K.ERROR_DEVICE, K.ERROR_OUT_OF_MEMORY):
             raise BluError(s, h.last_error())
+    return out
+
+
+def solve_sparse_batch(handles, irhs, xrhs, trans="N"):
+    """BLU.solve_sparse for len(handles) handles of one device in one call (one wave per member; per member the status,
+    pattern, values and flop counters of the single call, bit for bit).
+
+    irhs[k] / xrhs[k]: member k's sparse right-hand side; trans applies to every member.  Each handle's previous solution
+    is cleared and the new one left in h.lhs / h.ilhs[0..h.nzlhs), as BLU.solve_sparse does.  Returns the per-member
+    statuses.  A refused call raises BluError, as does ERROR_DEVICE or ERROR_OUT_OF_MEMORY of a member; the other codes
+    are only reported in the member's status."""
+    n = len(handles)
+    if len(irhs) != n or len(xrhs) != n:
+        raise ValueError("solve_sparse_batch: one right-hand side per handle")
+    L = lib()
+    L.blu_hip_solve_sparse_batch.argtypes = [C.c_void_p, C.c_int] + [C.c_void_p] * 6 + [C.c_char, C.c_void_p]
+    N = max(n, 1)
+    hs = (C.c_void_p * N)(*[h._h for h in handles])
+    irs = [np.ascontiguousarray(a, dtype=np.uint64) for a in irhs]
+    xrs = [np.ascontiguousarray(a, dtype=np.float64) for a in xrhs]
+    for k in range(n):
+        if irs[k].shape != xrs[k].shape or irs[k].ndim != 1:
+            raise ValueError("solve_sparse_batch: member %d: irhs and xrhs need equal lengths" % k)
+    nzr = (C.c_int64 * N)(*[len(a) for a in irs])
+    pi, px, pil, pl = (C.c_void_p * N)(), (C.c_void_p * N)(), (C.c_void_p * N)(), (C.c_void_p * N)()
+    for k, h in enumerate(handles):
+        h._clear_lhs()
+        pi[k], px[k] = irs[k].ctypes.data or None, xrs[k].ctypes.data or None  # (an empty right-hand side may pass NULL)
+        pil[k], pl[k] = h.ilhs.ctypes.data, h.lhs.ctypes.data or 8  # (m == 0: any non-NULL pointer)
+    nzl = (C.c_int64 * N)()
+    st = (C.c_int * N)()
+    rc = L.blu_hip_solve_sparse_batch(hs, n, nzr, pi, px, nzl, pil, pl, trans.encode()[0:1], st)
+    _refused(rc, handles, "solve_sparse_batch")
+    out = [int(s) for s in st][:n]
+    for k, (h, s) in enumerate(zip(handles, out)):
+        if s in (K.ERROR_DEVICE, K.ERROR_OUT_OF_MEMORY):
+            raise BluError(s, h.last_error())
+        if s == K.OK:
+            h.nzlhs = int(nzl[k])
     return out
 
 

@@ -153,13 +153,16 @@ static void ensure_upd_batch(blu_hip *h0, blu_hip **hs, std::vector<int> &list, 
 }
 
 // the storage-request loop over the members in `active` (run_solve_upd / the loop of blu_hip_update for one handle):
-// kind 0 = k_solve_upd_batch, 1 = k_update_batch.  mem[k] is what member k is handed (marker filled in here); on return
+// kind 0 = k_solve_upd_batch as solve_for_update (mode 1), 1 = k_update_batch, 2 = k_solve_upd_batch as solve_sparse
+// (mode 0: blu_solve_sparse_batch.inc).  mem[k] is what member k is handed (marker filled in here); on return
 // result[k] is set for every member and, for a solve that ended well, out[k] holds its counters.
 static void run_upd_batch(blu_hip *h0, blu_hip **hs, std::vector<int> active, std::vector<int> &result, int kind, int tr,
                           const std::vector<UpdMember> &mem, const std::vector<int> &ir, const std::vector<double> &xr,
                           const std::vector<size_t> &rhs_off, std::vector<UpdResult> &out)
 {
-    const char *what = kind ? "k_update_batch" : "k_solve_upd_batch";
+    const bool upd = kind == 1;
+    const int mode = kind == 0 ? 1 : 0;
+    const char *what = upd ? "k_update_batch" : "k_solve_upd_batch";
     for (int attempt = 0; attempt < 64 && !active.empty(); attempt++) {
         UpdRound R;
         for (int k : active) {
@@ -177,15 +180,15 @@ static void run_upd_batch(blu_hip *h0, blu_hip **hs, std::vector<int> active, st
         active.clear();
         if (R.list.empty()) break;
         int st;
-        if (kind)
+        if (upd)
             st = run_upd_round(h0, hs, R, ir, xr, rhs_off, what,
                                [](int c, hipStream_t stream, const DevLU *dD, const FinishOut *, const SparseWs *dW, const UpdWs *dU,
                                   const UpdMember *dM, UpdResult *dR) { hipLaunchKernelGGL(k_update_batch, dim3(c), dim3(64), 0, stream, dD, dW, dU, dM, dR); });
         else
             st = run_upd_round(h0, hs, R, ir, xr, rhs_off, what,
-                               [tr](int c, hipStream_t stream, const DevLU *dD, const FinishOut *, const SparseWs *dW, const UpdWs *dU,
+                               [mode, tr](int c, hipStream_t stream, const DevLU *dD, const FinishOut *, const SparseWs *dW, const UpdWs *dU,
                                     const UpdMember *dM, UpdResult *dR) {
-                                   hipLaunchKernelGGL(k_solve_upd_batch, dim3(c), dim3(64), 0, stream, dD, dW, dU, dM, dR, tr);
+                                   hipLaunchKernelGGL(k_solve_upd_batch, dim3(c), dim3(64), 0, stream, dD, dW, dU, dM, dR, mode, tr);
                                });
         if (st != BLU_OK) {
             fail_members(h0, hs, R.list, result, st);
@@ -198,14 +201,14 @@ static void run_upd_batch(blu_hip *h0, blu_hip **hs, std::vector<int> active, st
             h->ust = R.res[s].st;
             const int us = h->ust.status;
             if (us == UPD_OK) {
-                if (kind) h->nupdate++;
+                if (upd) h->nupdate++;
                 out[(size_t)k] = R.res[s];
                 result[k] = BLU_OK;
-            } else if (kind && us == UPD_SINGULAR) {
+            } else if (upd && us == UPD_SINGULAR) {
                 result[k] = BLU_ERROR_SINGULAR_UPDATE; // the old factorization is still valid
             } else if (us == UPD_ERROR) {
                 char buf[128];
-                snprintf(buf, sizeof buf, "%s: invariant violated at kernel source line %d", kind ? "update" : "update path", h->ust.err_line);
+                snprintf(buf, sizeof buf, "%s: invariant violated at kernel source line %d", upd ? "update" : "update path", h->ust.err_line);
                 h->err = buf;
                 h->nupdate = -1; // the factors may be half modified: invalid from here on
                 result[k] = BLU_ERROR_DEVICE;
@@ -217,12 +220,12 @@ static void run_upd_batch(blu_hip *h0, blu_hip **hs, std::vector<int> active, st
         }
     }
     for (int k : active) {
-        hs[k]->err = kind ? "update: too many storage requests" : "update path: too many storage requests";
+        hs[k]->err = upd ? "update: too many storage requests" : "update path: too many storage requests";
         result[k] = BLU_ERROR_DEVICE;
     }
 }
 
-// the refusals the two entries share; BLU_OK = go on
+// the refusals the batch entries of the update path and blu_hip_solve_sparse_batch share; BLU_OK = go on
 static int upd_batch_refusal(blu_hip **hs, int n)
 {
     for (int k = 0; k < n; k++)

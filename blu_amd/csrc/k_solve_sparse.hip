@@ -363,12 +363,12 @@ __device__ __forceinline__ void sweep_nonzeros_desc(int len, const double *vec, 
     }
 }
 
-__global__ void __launch_bounds__(64) k_solve_sparse(DevLU *Ds, FinishOut *Os, SparseWs W, int nrhs, const int *irhs, const double *xrhs,
-                                                     int trans, int marker, int nz_sparse)
+// solve_sparse on a fresh factorization, whole wave: the body of k_solve_sparse and of k_solve_sparse_batch
+// (k_update.hip).  Leaves W.out[0] nzlhs, [1] l_flops, [2] u_flops, [3] branch taken (1 sparse, 2 sequential).
+__device__ __forceinline__ void solve_sparse_wave(const DevG &D, const FinishOut &O, const SparseWs &W, int nrhs, const int *irhs,
+                                                  const double *xrhs, int trans, int marker, int nz_sparse, DfsRing *R)
 {
-    __shared__ DfsRing dfs_ring;
-    const DevG D(Ds[0]);
-    const FinishOut &O = Os[0];
+    DfsRing &dfs_ring = *R;
     const int lane = lane_id();
     const int m = D.m;
     const int rank = D.s->rank;
@@ -505,6 +505,12 @@ __global__ void __launch_bounds__(64) k_solve_sparse(DevLU *Ds, FinishOut *Os, S
         W.out[2] = u_flops;
         W.out[3] = branch;
     }
+}
+__global__ void __launch_bounds__(64) k_solve_sparse(DevLU *Ds, FinishOut *Os, SparseWs W, int nrhs, const int *irhs, const double *xrhs,
+                                                     int trans, int marker, int nz_sparse)
+{
+    __shared__ DfsRing dfs_ring;
+    solve_sparse_wave(DevG(Ds[0]), Os[0], W, nrhs, irhs, xrhs, trans, marker, nz_sparse, &dfs_ring);
 }
 
 // Row-wise L in the reference's order (build_factors.rs:243-274): row i holds, for every column it has

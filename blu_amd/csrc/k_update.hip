@@ -1019,16 +1019,35 @@ __global__ void __launch_bounds__(1024) k_upd_init_batch(const DevLU *Ds, const 
     }
 }
 
+// mode 1: solve_for_update (blu_hip_solve_for_update_batch); mode 0: solve_sparse on an updated factorization
+// (blu_hip_solve_sparse_batch)
 __global__ void __launch_bounds__(64) k_solve_upd_batch(const DevLU *Ds, const SparseWs *Ws, const UpdWs *Us, const UpdMember *Ms, UpdResult *Rs,
-                                                        int trans)
+                                                        int mode, int trans)
 {
     __shared__ DfsRing dfs_ring;
     const int b = blockIdx.x;
     const UpdMember M = Ms[b];
     const SparseWs W = Ws[b];
     const UpdWs U = Us[b];
-    solve_upd_wave(DevG(Ds[b]), W, U, 1, M.want_solution, M.nrhs, M.irhs, M.xrhs, trans, M.marker, M.nz_sparse, &dfs_ring);
+    solve_upd_wave(DevG(Ds[b]), W, U, mode, M.want_solution, M.nrhs, M.irhs, M.xrhs, trans, M.marker, M.nz_sparse, &dfs_ring);
     upd_result_lane0(W, U, &Rs[b], true);
+}
+
+// solve_sparse on the fresh factorizations of blu_hip_solve_sparse_batch: the body of k_solve_sparse (k_solve_sparse.hip),
+// one wave per member.  There is no UpdState here: Rs[b].out[0..3] alone are written ([4] = 0, a fresh solve has no
+// row etas), by the lane that wrote W.out.
+__global__ void __launch_bounds__(64) k_solve_sparse_batch(const DevLU *Ds, const FinishOut *Os, const SparseWs *Ws, const UpdMember *Ms,
+                                                           UpdResult *Rs, int trans)
+{
+    __shared__ DfsRing dfs_ring;
+    const int b = blockIdx.x;
+    const UpdMember M = Ms[b];
+    const SparseWs W = Ws[b];
+    solve_sparse_wave(DevG(Ds[b]), Os[b], W, M.nrhs, M.irhs, M.xrhs, trans, M.marker, M.nz_sparse, &dfs_ring);
+    if (lane_id() == 0) {
+        for (int q = 0; q < 4; q++) Rs[b].out[q] = W.out[q];
+        Rs[b].out[4] = 0;
+    }
 }
 
 __global__ void __launch_bounds__(64) k_update_batch(const DevLU *Ds, const SparseWs *Ws, const UpdWs *Us, const UpdMember *Ms, UpdResult *Rs)

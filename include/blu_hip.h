@@ -243,6 +243,29 @@ int blu_hip_solve_for_update_batch(blu_hip **h, int n, const int64_t *nzrhs, con
                                    char trans, int *status);
 int blu_hip_update_batch(blu_hip **h, int n, const double *xtbl, int *status);
 
+/* Batch extension: blu_hip_solve_sparse for n handles on one device in one call.  Member k gets exactly what
+ * blu_hip_solve_sparse(h[k], nzrhs[k], irhs[k], xrhs[k], &nzlhs[k], ilhs[k], lhs[k], trans) gives: status, nzlhs, the
+ * pattern in the reference's order, the bits of the values, BLU_STAT_L_FLOPS / U_FLOPS / R_FLOPS, the branch taken and
+ * the handle's later behaviour (marker, all-zero work vectors, the row-wise L kept for later calls).  lhs[k] is all
+ * zero on entry, as for the single call; trans applies to every member.  Each member runs on ONE wave, the members of
+ * a kind in one launch (k_solve_sparse_batch for a fresh factorization, k_solve_upd_batch after updates), and the call
+ * costs, whatever n is: one upload (descriptors and every right-hand side, packed), the launches, one synchronize, one
+ * download of the counters, one gather launch (k_gather_lhs_batch) and one download of the gathered solutions, which
+ * the host scatters into lhs[k] / ilhs[k].  A transposed call builds the row-wise L of the fresh members that lack it
+ * in one launch first (k_build_lt_batch).  The kernels keep 24 KB of LDS per member in flight, so about 6 members per
+ * CU run at once and the rest follow inside the same launch.
+ * Refused as a whole, every status[k] carrying the code and no handle touched: NULL h, nzrhs, nzlhs, ilhs, lhs, a NULL
+ * handle, ilhs[k] or lhs[k], n < 0, NULL irhs / xrhs or a NULL irhs[k] / xrhs[k] of a member with nzrhs[k] > 0
+ * (BLU_ERROR_ARGUMENT_MISSING); the same handle twice or handles on different devices (BLU_ERROR_INVALID_ARGUMENT).
+ * n == 0 returns BLU_OK and writes nothing.  Everything else is per member, checked in the order of the single entry,
+ * and the other members run regardless: BLU_ERROR_INVALID_CALL without a valid factorization,
+ * BLU_ERROR_INVALID_ARGUMENT for nzrhs[k] < 0, nzrhs[k] > m or an index out of range, BLU_OK with nzlhs[k] = 0 for
+ * m == 0, BLU_ERROR_OUT_OF_MEMORY, BLU_ERROR_DEVICE.  status may be NULL.  Returns the most negative member status,
+ * else the largest.  Several right-hand sides for ONE handle need one call each: a handle has one workspace. */
+int blu_hip_solve_sparse_batch(blu_hip **h, int n, const int64_t *nzrhs, const uint64_t *const *irhs,
+                               const double *const *xrhs, int64_t *nzlhs, int64_t *const *ilhs, double *const *lhs,
+                               char trans, int *status);
+
 /* factorize() ends with the statistics tail of src/factorize.rs:121-147 (condest(L), condest(U),
  * residual_test; getters BLU_STAT_CONDEST_* .. BLU_STAT_RESIDUAL_TEST).  It is a chain of 8 triangular
  * sweeps (~17 % of the factorize time at 100k); a caller that never reads those getters can switch

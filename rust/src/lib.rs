@@ -72,6 +72,10 @@ extern "C" {
         ilhs: *const *mut i64, lhs: *const *mut f64, trans: c_char, status: *mut c_int,
     ) -> c_int;
     fn blu_hip_update_batch(h: *mut *mut BluHip, n: c_int, xtbl: *const c_double, status: *mut c_int) -> c_int;
+    fn blu_hip_solve_sparse_batch(
+        h: *mut *mut BluHip, n: c_int, nzrhs: *const i64, irhs: *const *const u64, xrhs: *const *const f64, nzlhs: *mut i64,
+        ilhs: *const *mut i64, lhs: *const *mut f64, trans: c_char, status: *mut c_int,
+    ) -> c_int;
     fn blu_hip_last_error(h: *const BluHip) -> *const c_char;
 }
 
@@ -441,6 +445,49 @@ pub fn update_batch(blus: &mut [&mut BLU], xtbl: &[f64]) -> Result<Vec<Result<()
     let code = unsafe { blu_hip_update_batch(hs.as_mut_ptr(), n as c_int, xtbl.as_ptr(), st.as_mut_ptr()) };
     if code == -3 || (code == -4 && blus.iter().any(|b| b.device != blus[0].device)) {
         return status_of(code).map(|_| Vec::new());
+    }
+    Ok(st.iter().map(|&s| status_of(s)).collect())
+}
+
+/// `BLU::solve_sparse` for many objects of one device in one call (batch extension, no reference counterpart): member k
+/// gets what `blus[k].solve_sparse(irhs[k].len(), irhs[k], xrhs[k], trans)` gives, its solution left in `blus[k].lhs` /
+/// `ilhs[..nzlhs]`.  `Err` is a refusal of the whole call (the same object twice cannot be expressed here; objects on two
+/// devices); otherwise one result per member.
+pub fn solve_sparse_batch(blus: &mut [&mut BLU], irhs: &[&[usize]], xrhs: &[&[f64]], trans: char) -> Result<Vec<Result<(), Status>>, Status> {
+    let n = blus.len();
+    if irhs.len() != n || xrhs.len() != n {
+        return Err(Status::ErrorInvalidArgument);
+    }
+    // the C side reads irhs[k][0..nzrhs[k]) and xrhs[k][0..nzrhs[k]): never hand it a count beyond the slices
+    if (0..n).any(|k| xrhs[k].len() < irhs[k].len()) {
+        return Err(Status::ErrorInvalidArgument);
+    }
+    for b in blus.iter_mut() {
+        b.clear_lhs();
+    }
+    let mut hs: Vec<*mut BluHip> = blus.iter().map(|b| b.lu.h).collect();
+    let nzrhs: Vec<i64> = irhs.iter().map(|x| x.len() as i64).collect();
+    // (an empty right-hand side may pass NULL for both arrays, as the single call allows)
+    let ip: Vec<*const u64> = irhs.iter().map(|x| if x.is_empty() { std::ptr::null() } else { x.as_ptr() as *const u64 }).collect();
+    let xp: Vec<*const f64> = xrhs.iter().zip(irhs).map(|(x, i)| if i.is_empty() { std::ptr::null() } else { x.as_ptr() }).collect();
+    let il: Vec<*mut i64> = blus.iter_mut().map(|b| b.ilhs.as_mut_ptr()).collect();
+    let lp: Vec<*mut f64> = blus.iter_mut().map(|b| b.lhs.as_mut_ptr()).collect();
+    let mut nz = vec![0i64; n];
+    let mut st = vec![0 as c_int; n];
+    let code = unsafe {
+        blu_hip_solve_sparse_batch(
+            hs.as_mut_ptr(), n as c_int, nzrhs.as_ptr(), ip.as_ptr(), xp.as_ptr(), nz.as_mut_ptr(), il.as_ptr(), lp.as_ptr(), trans as c_char,
+            st.as_mut_ptr(),
+        )
+    };
+    // -3 is returned by a refusal alone; -4 is also a member's status (an index out of range): a refusal only for two devices
+    if code == -3 || (code == -4 && blus.iter().any(|b| b.device != blus[0].device)) {
+        return status_of(code).map(|_| Vec::new());
+    }
+    for k in 0..n {
+        if st[k] == 0 {
+            blus[k].nzlhs = nz[k] as usize;
+        }
     }
     Ok(st.iter().map(|&s| status_of(s)).collect())
 }
