@@ -117,6 +117,10 @@ typedef struct orc_lu {
     lu_int nunsymperm_total; /* updates done by an unsymmetric permutation (test hook; no counter in the reference) */
     lu_int npivot_kind[6]; /* pivots taken per path: 0 singleton row, 1 singleton col, 2 doubleton col,
                               3 small, 4 any, 5 empty column (factorize_bump.rs:24-33) */
+    lu_int ncancel[4]; /* entries that elimination cancelled, per path (test hook; the tests on
+                          integer-valued bases prove with them that their inputs reach each branch):
+                          0 exact zeros that pivot_any stored in a column; with |x| <= droptol: 1 pivot_small cancellations (mask bits),
+                          2 doubleton fill-in dropped, 3 doubleton cancellations (marked[j] = 1) */
     lu_int stop_after_pivots; /* <0: off; else factorize_bump returns
                                  ORC_STOPPED once rank+rankdef reaches it */
 } orc_lu;

@@ -59,6 +59,8 @@ def lib():
         L.orc_dbg_set_fix_d3.argtypes = [C.c_void_p, C.c_int]
         L.orc_dbg_d3_hits.restype = C.c_int64
         L.orc_dbg_d3_hits.argtypes = [C.c_void_p]
+        L.orc_dbg_ncancel.restype = C.c_int64
+        L.orc_dbg_ncancel.argtypes = [C.c_void_p, C.c_int]
         L.orc_dbg_active_state.argtypes = [C.c_void_p] + [C.c_void_p] * 12
         L.orc_dbg_active_nnz.restype = C.c_int64
         L.orc_dbg_active_nnz.argtypes = [C.c_void_p, C.c_int]
@@ -207,6 +209,15 @@ class OracleBLU:
 
     def d3_hits(self):
         return int(lib().orc_dbg_d3_hits(self._lu))
+
+    CANCEL_PATHS = ("any_stored", "small", "doubleton_fill", "doubleton")
+
+    def cancellations(self):
+        """Entries that elimination cancelled in the last factorization, per path: exact zeros that pivot_any kept as
+        stored values ("any_stored"); with |x| <= droptol, what pivot_small took out through its mask ("small"), fill-in that
+        pivot_doubleton_col dropped ("doubleton_fill") and entries it cancelled ("doubleton").  No device counterpart:
+        the tests use them to prove that an input reaches a branch."""
+        return {name: int(lib().orc_dbg_ncancel(self._lu, k)) for k, name in enumerate(self.CANCEL_PATHS)}
 
     def active_state(self):
         """Layout-independent dump of the active submatrix between two pivots."""

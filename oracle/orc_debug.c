@@ -6,6 +6,8 @@
 void orc_dbg_set_stop(orc_lu *lu, lu_int npivots) { lu->stop_after_pivots = npivots; }
 void orc_dbg_set_fix_d3(orc_lu *lu, int on) { lu->fix_d3 = on; }
 lu_int orc_dbg_d3_hits(const orc_lu *lu) { return lu->d3_hits; }
+/* path: 0 pivot_any stored zeros, 1 pivot_small cancellations, 2 doubleton fill drops, 3 doubleton cancellations */
+lu_int orc_dbg_ncancel(const orc_lu *lu, int path) { return path >= 0 && path < 4 ? lu->ncancel[path] : -1; }
 
 /* which: 0 = column file entries, 1 = row file entries (valid while task == FACTORIZE_BUMP) */
 lu_int orc_dbg_active_nnz(const orc_lu *lu, int which)

@@ -234,6 +234,7 @@ static int pivot_any(orc_lu *lu)
             put++;
             double x = fabs(work[pos]);
             if (x > cmx) cmx = x;
+            if (x == 0.0) lu->ncancel[0]++; /* test hook: pivot_any keeps the entry as a stored zero */
             work[pos] = 0.0;
         }
         w_end[j] = put;
@@ -436,6 +437,7 @@ static int pivot_small(orc_lu *lu)
                 mask |= (int32_t)((uint32_t)1 << (unsigned)((pos - 1) & 31));
                 mask64 |= (int64_t)((uint64_t)1 << (unsigned)(pos - 1));
                 if (pos - 1 >= 31) lu->d3_hits++;
+                lu->ncancel[1]++;
             }
             work[pos] = 0.0;
         }
@@ -780,6 +782,7 @@ static int pivot_doubleton_col(orc_lu *lu)
                 if (xabs > cmx) cmx = xabs;
             } else {
                 /* Remove pivot row entry. */
+                lu->ncancel[2]++;
                 w_end[j]--;
                 end = w_end[j];
                 w_index[where_pivot] = w_index[end];
@@ -806,6 +809,7 @@ static int pivot_doubleton_col(orc_lu *lu)
                 w_value[where_other] = w_value[end];
                 marked[j] = 1;
                 ncancelled++;
+                lu->ncancel[3]++;
             } else if (x > cmx) {
                 cmx = x;
             }

@@ -156,6 +156,7 @@ void orc_lu_reset(orc_lu *lu)
     lu->pivot_error = 0.0;
     lu->d3_hits = 0; /* test hook counter, not in the reference */
     for (int k = 0; k < 6; k++) lu->npivot_kind[k] = 0;
+    for (int k = 0; k < 4; k++) lu->ncancel[k] = 0;
 
     lu->task = ORC_TASK_NONE;
     lu->pivot_row = -1;

@@ -98,18 +98,23 @@ def _same(a, b, what):
         assert np.array_equal(a[2], b[2]), (what, "values", np.abs(a[2] - b[2]).max())
 
 
-def run_updates(h, cols, m, nupd, rng, refactor=None, check_every=1, stop_on_max=False, tol_xtbl=1e-3, pair_row=None, twin=None):
+def run_updates(h, cols, m, nupd, rng, refactor=None, check_every=1, stop_on_max=False, tol_xtbl=1e-3, pair_row=None, twin=None,
+                column_source=None, on_step=None):
     """Returns a log dict; `cols` is modified in place to the current basis.  Replacements whose pivot
     |xtbl| = |(B^-1 a)_j| is below tol_xtbl are not applied (they would make the basis ill-conditioned and the
     residual checks meaningless).  pair_row[j] = row paired with column j in the INITIAL factorization.
     twin: a second object (the CPU restatement of the same intended algorithm) driven in lockstep; every status,
-    pattern and value must be identical to h's."""
+    pattern and value must be identical to h's.
+    column_source: called like new_column (the default) for the incoming column of position j.
+    on_step(event, **what): called with the matrix B the factorization stands for at that moment, after the transposed
+    solve ("btran": j, il, x, B), after the forward solve ("ftran": j, ai, ax, il, x, B) and after update() ("update": j,
+    status, B -- the new B when the status is OK): checks of a caller on top of those made here."""
     log = dict(done=0, skipped=0, singular=0, max_residual=0.0, max_vs_fresh=0.0, max_pivot_error=0.0, hit_maximum_updates=False,
                max_sparse_diff=0.0)
     B = matrix_of(cols, m)
     for step in range(nupd):
         j = int(rng.integers(0, m))
-        ai, ax = new_column(rng, cols, m, j, pair_row)
+        ai, ax = (column_source or new_column)(rng, cols, m, j, pair_row)
         st, il, row = _sfu(h, [j], None, "T")
         if twin is not None:
             _same((st, il, row), _sfu(twin, [j], None, "T"), ("solve_for_update T", step))
@@ -124,6 +129,8 @@ def run_updates(h, cols, m, nupd, rng, refactor=None, check_every=1, stop_on_max
         ej[j] = 1.0
         log["max_residual"] = max(log["max_residual"], backward_error(B.T, row, ej))
         assert np.array_equal(np.sort(il), np.flatnonzero(row)), "pattern of the transposed solution"
+        if on_step is not None:
+            on_step("btran", j=j, il=il, x=row, B=B)
         st, il2, lhs = _sfu(h, ai, ax, "N")
         if twin is not None:
             _same((st, il2, lhs), _sfu(twin, ai, ax, "N"), ("solve_for_update N", step))
@@ -132,6 +139,8 @@ def run_updates(h, cols, m, nupd, rng, refactor=None, check_every=1, stop_on_max
         a[ai] = ax
         log["max_residual"] = max(log["max_residual"], backward_error(B, lhs, a))
         assert np.array_equal(np.sort(il2), np.flatnonzero(lhs)), "pattern of the forward solution"
+        if on_step is not None:
+            on_step("ftran", j=j, ai=ai, ax=ax, il=il2, x=lhs, B=B)
         xtbl = lhs[j]
         if abs(xtbl) < tol_xtbl:
             log["skipped"] += 1
@@ -144,12 +153,16 @@ def run_updates(h, cols, m, nupd, rng, refactor=None, check_every=1, stop_on_max
                 assert h.stat(key) == twin.stat(key), ("stat", key, step, h.stat(key), twin.stat(key))
         if st == K.ERROR_SINGULAR_UPDATE:
             log["singular"] += 1
+            if on_step is not None:
+                on_step("update", j=j, status=st, B=B)
             continue
         assert st == K.OK, st
         log["done"] += 1
         log["max_pivot_error"] = max(log["max_pivot_error"], h.stat(K.STAT_PIVOT_ERROR))
         cols[j] = (ai, ax)
         B = matrix_of(cols, m)
+        if on_step is not None:
+            on_step("update", j=j, status=st, B=B)
         if log["done"] % check_every == 0:
             b = rng.standard_normal(m)
             x = h.solve_dense(b, "N")
