@@ -9,6 +9,7 @@ with the same method names, argument meaning and error behaviour:
     .factorize(b_begin, b_end, b_i, b_x)           BLU::factorize           blu.rs:95
     .get_factors()                                 BLU::get_factors         blu.rs:139
     .solve_dense(rhs, trans)                       BLU::solve_dense         blu.rs:182
+    .solve_dense_multi(rhs, trans)                 solve_dense for many right-hand sides on one handle in one call
     solve_dense_batch(handles, rhs, trans)         solve_dense for many handles in one call (batch extension)
     solve_for_update_batch(handles, irhs, xrhs)    solve_for_update for many handles in one call (batch extension)
     update_batch(handles, xtbl)                    update for many handles in one call (batch extension)
@@ -42,7 +43,7 @@ EXPORTS = [
     "blu_hip_factorize_batch", "blu_hip_version", "blu_hip_device_count", "blu_hip_last_error",
     "blu_hip_solve_sparse", "blu_hip_solve_for_update", "blu_hip_update", "blu_hip_set_skip_stats", "blu_hip_gen_lp_basis",
     "blu_hip_solve_dense_batch", "blu_hip_solve_for_update_batch", "blu_hip_update_batch",
-    "blu_hip_solve_sparse_batch",
+    "blu_hip_solve_sparse_batch", "blu_hip_solve_dense_multi",
 ]
 
 
@@ -411,6 +412,33 @@ class BLU:
             raise BluError(st, self.last_error())
         return lhs
 
+    def solve_dense_multi(self, rhs=None, trans="N", device_ptrs=None):
+        """solve_dense for many right-hand sides on this handle in one call (one wave per right-hand side, the factors
+        shared; every solution bit-identical to solve_dense on the same right-hand side).
+
+        rhs: (nrhs, m) host array, row j the j-th right-hand side.  Returns the (nrhs, m) solutions.
+        device_ptrs: (p_rhs, ldrhs, p_lhs, ldlhs, nrhs) raw device pointers (e.g. torch tensors' data_ptr()) and leading
+            dimensions in doubles: right-hand side j at p_rhs + 8*j*ldrhs, solution j at p_lhs + 8*j*ldlhs; p_rhs == p_lhs
+            with equal leading dimensions is allowed.  Returns nothing.
+        Errors raise BluError, as solve_dense does."""
+        L = lib()
+        L.blu_hip_solve_dense_multi.argtypes = [C.c_void_p, C.c_int64, C.c_void_p, C.c_int64, C.c_void_p, C.c_int64, C.c_char, C.c_int]
+        tr = trans.encode()[0:1]
+        if device_ptrs is not None:
+            p_rhs, ldrhs, p_lhs, ldlhs, nrhs = device_ptrs
+            st = L.blu_hip_solve_dense_multi(self._h, int(nrhs), int(p_rhs), int(ldrhs), int(p_lhs), int(ldlhs), tr, 1)
+            if st != K.OK:
+                raise BluError(st, self.last_error())
+            return None
+        r = np.ascontiguousarray(rhs, dtype=np.float64)
+        if r.ndim != 2 or r.shape[1] != self.m:
+            raise ValueError("solve_dense_multi: rhs needs the shape (nrhs, m = %d)" % self.m)
+        lhs = np.zeros(r.shape)
+        st = L.blu_hip_solve_dense_multi(self._h, r.shape[0], r.ctypes.data or 8, self.m, lhs.ctypes.data or 8, self.m, tr, 0)
+        if st != K.OK:
+            raise BluError(st, self.last_error())
+        return lhs
+
     # --- BLU::solve_sparse (blu.rs:207) ------------------------------------------------------------
     def solve_sparse(self, irhs, xrhs, trans="N"):
         """Sparse right-hand side irhs/xrhs -> solution.  As in the reference the result stays in the
@@ -497,6 +525,18 @@ class BLU:
         """Arena slack of the update path (entries); small values force the host-side growth loop."""
         lib().blu_hip_dbg_set_upd_extra.argtypes = [C.c_void_p, C.c_int64]
         lib().blu_hip_dbg_set_upd_extra(self._h, int(n))
+
+    def dbg_set_multi_ws_bytes(self, n):
+        """Byte limit of the work vectors plus staging block of solve_dense_multi (-1: the default, 1 GiB); small values
+        force the chunking at small shapes."""
+        lib().blu_hip_dbg_set_multi_ws_bytes.argtypes = [C.c_void_p, C.c_int64]
+        lib().blu_hip_dbg_set_multi_ws_bytes(self._h, int(n))
+
+    def dbg_multi_last_chunk(self):
+        """Right-hand sides per chunk of the last solve_dense_multi."""
+        lib().blu_hip_dbg_multi_last_chunk.restype = C.c_int64
+        lib().blu_hip_dbg_multi_last_chunk.argtypes = [C.c_void_p]
+        return int(lib().blu_hip_dbg_multi_last_chunk(self._h))
 
     def dbg_set_grid_blocks(self, n):
         """Workgroups of the chip-wide O(nnz) phases of a single factorize (1 = one workgroup, as inside a batch)."""

@@ -91,6 +91,12 @@ struct blu_hip {
     int64_t upd_alloc_m;    // m the fixed-size arrays of uw were allocated for (-1: none)
     int64_t upd_for_nfact;  // nfactorize uw was built for (-1: none)
     int64_t upd_extra;      // debug: arena slack of the update path (-1: default)
+    // blu_hip_solve_dense_multi (blu_solve_multi.inc): one work vector per right-hand side in flight, and the staging block of
+    // host inputs; allocated at the first call, grown on demand
+    double *mws, *mio;
+    int64_t mws_cols, mio_cols;  // columns (of multi_stride doubles) they hold
+    int64_t multi_ws_bytes;      // debug: byte limit of the two together (-1: default)
+    int64_t multi_last_chunk;    // columns per chunk of the last call
     int64_t sp_l_flops, sp_u_flops; // lu.l_flops / lu.u_flops
     int sp_branch;                  // 1 sparse, 2 sequential: branch of the last solve_sparse (diagnostic)
     // timing
@@ -158,6 +164,7 @@ template <class T> static bool dgrow(blu_hip *h, T **p, size_t keep, size_t n)
 static const int64_t kIntMax = 0x7ffffff0;
 
 static void free_upd(blu_hip *h);
+static void free_multi(blu_hip *h);
 static void free_all(blu_hip *h)
 {
     DevLU &D = h->D;
@@ -174,6 +181,7 @@ static void free_all(blu_hip *h)
     dfree(h->d_rhs); dfree(h->d_lhs); dfree(D.gwork);
     dfree(h->ur_len); dfree(h->ur_pos); dfree(h->ur_val);
     free_upd(h);
+    free_multi(h);
     // everything else lives in the slab
     dfree(h->slab);
 }
@@ -258,6 +266,10 @@ extern "C" blu_hip *blu_hip_new(int64_t m, int64_t b_nz, int device)
     h->upd_alloc_m = -1;
     h->upd_for_nfact = -1;
     h->upd_extra = -1;
+    h->mws = h->mio = nullptr;
+    h->mws_cols = h->mio_cols = 0;
+    h->multi_ws_bytes = -1;
+    h->multi_last_chunk = 0;
     h->chain_ok = 0;
     h->chain_defects = 0;
     h->ur_len = h->ur_pos = nullptr;
@@ -893,6 +905,7 @@ extern "C" int blu_hip_solve_dense(blu_hip *h, const double *rhs, double *lhs, c
 }
 
 #include "blu_solve_batch.inc"
+#include "blu_solve_multi.inc"
 #include "blu_update_batch.inc"
 #include "blu_solve_sparse_batch.inc"
 

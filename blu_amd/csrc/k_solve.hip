@@ -1,5 +1,6 @@
 // k_solve.hip -- solve_dense (src/lu/solve_dense.rs:7-120) for a fresh factorization (nforrest = 0),
-// one workgroup per matrix (k_solve_dense), or one wave per member of a batch (k_solve_dense_batch).
+// one workgroup per matrix (k_solve_dense), one wave per member of a batch (k_solve_dense_batch), or one wave per
+// right-hand side of ONE factorization (k_solve_dense_multi).
 //
 // The reference's operation order is kept exactly, so the solution is bit-identical to it:
 //   forward     L: for k ascending   x = sum over ROW pivotrow[k] of L (row-wise copy, ascending in the
@@ -119,14 +120,14 @@ struct WRows {
     }
 };
 
-// the two sweeps of one system on ONE wave: y = D.txrj holds the right-hand side (m+2 doubles of scratch: work1)
-__device__ __forceinline__ void solve_dense_sweeps(const DevG &D, const FinishOut &O, double *lhs, int trans, const int *lt_ptr,
+// the two sweeps of one system on ONE wave: y holds the right-hand side (m+2 doubles of scratch: work1) -- D.txrj, the
+// handle's own work vector, or one of the per-column work vectors of blu_hip_solve_dense_multi
+__device__ __forceinline__ void solve_dense_sweeps(const DevG &D, const FinishOut &O, gdouble_p y, double *lhs, int trans, const int *lt_ptr,
                                                    const int *lt_idx, const double *lt_val)
 {
     const int lane = lane_id();
     const int m = D.m;
     const int rank = D.s->rank;
-    gdouble_p y = D.txrj;
     gdouble_p x_out = (gdouble_p)lhs;
     const auto at_aux = [](int, const ColPtr &P) { return P.aux; };
     const auto at_aux2 = [](int, const ColPtr &P) { return P.aux2; };
@@ -165,7 +166,7 @@ __global__ void __launch_bounds__(1024) k_solve_dense(DevLU *Ds, FinishOut *Os, 
     for (int k = tid; k < m; k += nt) y[k] = rhs[k]; // solve_dense.rs:34 / :77
     __syncthreads();
     if (wave_id() != 0) return;
-    solve_dense_sweeps(D, Os[blockIdx.x], lhs, trans, lt_ptr, lt_idx, lt_val);
+    solve_dense_sweeps(D, Os[blockIdx.x], y, lhs, trans, lt_ptr, lt_idx, lt_val);
 }
 
 // ------------------------------------------------------------------------------------------------
@@ -192,5 +193,25 @@ __global__ void __launch_bounds__(64) k_solve_dense_batch(const DevLU *__restric
     gdouble_p y = D.txrj;
     for (int k = lane_id(); k < m; k += 64) y[k] = M.rhs[k]; // solve_dense.rs:34 / :77
     wave_mem_sync();
-    solve_dense_sweeps(D, Os[b], M.lhs, trans, M.lt_ptr, M.lt_idx, M.lt_val);
+    solve_dense_sweeps(D, Os[b], y, M.lhs, trans, M.lt_ptr, M.lt_idx, M.lt_val);
+}
+
+// ------------------------------------------------------------------------------------------------
+// blu_hip_solve_dense_multi: n right-hand sides on ONE fresh factorization, each on a workgroup of ONE wave.  The factors
+// are read-only and shared by every wave; wave j owns work vector j (ws + j * wstride, m + 2 doubles of it) and column j
+// of rhs / lhs (leading dimensions ldrhs / ldlhs; rhs == lhs with equal leading dimensions allowed).  The sweeps and
+// their line sets are those of k_solve_dense, so column j has the bits of the single call.
+// ------------------------------------------------------------------------------------------------
+__global__ void __launch_bounds__(64) k_solve_dense_multi(const DevLU *__restrict__ Ds, const FinishOut *__restrict__ Os, const double *rhs,
+                                                          long long ldrhs, double *lhs, long long ldlhs, double *ws, long long wstride,
+                                                          int trans, const int *lt_ptr, const int *lt_idx, const double *lt_val)
+{
+    const long long j = blockIdx.x;
+    const DevG D(Ds[0]);
+    const int m = D.m;
+    gdouble_p y = (gdouble_p)(ws + j * wstride);
+    const double *r = rhs + j * ldrhs;
+    for (int k = lane_id(); k < m; k += 64) y[k] = r[k]; // solve_dense.rs:34 / :77
+    wave_mem_sync();
+    solve_dense_sweeps(D, Os[0], y, lhs + j * ldlhs, trans, lt_ptr, lt_idx, lt_val);
 }

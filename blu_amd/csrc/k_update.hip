@@ -1173,3 +1173,24 @@ __global__ void __launch_bounds__(64) k_solve_dense_upd_batch(const DevLU *__res
     const SolveMember M = Ms[b];
     solve_dense_upd_wave(DevG(Ds[b]), Ws[b], Us[b], M.rhs, M.lhs, trans, M.marker);
 }
+
+// ---------------------------------------------------------------------------------------------------------
+// blu_hip_solve_dense_multi on an updated factorization: n right-hand sides on ONE handle, one wave each.
+// solve_dense_upd_wave begins with garbage_perm_wave, which rewrites pvcol / pvrow / marked and st->pivotlen of the
+// handle: k_garbage_perm does it ONCE, on one wave, in a launch of its own before the solves (same marker value as the
+// single call, marker + 1).  Afterwards pivotlen <= m, so the body's own call returns at once and the rest of the body
+// only READS the handle -- pvcol / pvrow, the row and column files of U, the row etas, both copies of L, st->nforrest --
+// and writes its work vector and its column of lhs (the work vector of the L' and eta sweeps of the transposed system).
+// Wave j runs it with a copy of UpdWs whose work1 is work vector j.
+// ---------------------------------------------------------------------------------------------------------
+__global__ void __launch_bounds__(64) k_garbage_perm(DevLU *Ds, SparseWs W, UpdWs U, int marker)
+{
+    garbage_perm_wave(U, DevG(Ds[0]).m, W.marked, marker + 1, W.estack); // solve_dense.rs:9
+}
+__global__ void __launch_bounds__(64) k_solve_dense_upd_multi(const DevLU *__restrict__ Ds, SparseWs W, UpdWs U, const double *rhs, long long ldrhs,
+                                                              double *lhs, long long ldlhs, double *ws, long long wstride, int trans, int marker)
+{
+    const long long j = blockIdx.x;
+    U.work1 = ws + j * wstride;
+    solve_dense_upd_wave(DevG(Ds[0]), W, U, rhs + j * ldrhs, lhs + j * ldlhs, trans, marker);
+}

@@ -222,6 +222,27 @@ int blu_hip_factorize_batch(blu_hip **h, int n,
 int blu_hip_solve_dense_batch(blu_hip **h, int n, const double *const *rhs, double *const *lhs, char trans,
                               int inputs_on_device, int *status);
 
+/* Several right-hand sides on ONE handle: blu_hip_solve_dense for nrhs right-hand sides in one call, column j bit-identical
+ * to blu_hip_solve_dense(h, rhs_j, lhs_j, trans), on fresh (rank-deficient included) and on updated factorizations.
+ * Right-hand side j is rhs[j*ldrhs .. j*ldrhs+m), solution j goes to lhs[j*ldlhs .. j*ldlhs+m); what lies between m and
+ * a leading dimension is neither read nor written.  rhs == lhs with ldrhs == ldlhs is allowed (in place); otherwise the
+ * two blocks must not overlap.  With inputs_on_device != 0 both are device pointers on the handle's device, else host
+ * arrays.  Each right-hand side runs on ONE wave with a work vector of its own, the factors are shared
+ * (k_solve_dense_multi; after updates k_garbage_perm once, then k_solve_dense_upd_multi).  Afterwards the handle is as
+ * after ONE blu_hip_solve_dense call: the row-wise L a forward solve built is kept, after updates the pivot sequence
+ * is compacted once and the marker advanced once, and later solve_sparse / solve_for_update / update calls continue
+ * exactly as they would have.
+ * Checked in this order: NULL h BLU_ERROR_ARGUMENT_MISSING; no valid factorization BLU_ERROR_INVALID_CALL; NULL rhs or
+ * lhs BLU_ERROR_ARGUMENT_MISSING; nrhs < 0, or ldrhs < m or ldlhs < m when nrhs > 1, BLU_ERROR_INVALID_ARGUMENT;
+ * nrhs == 0 or m == 0 BLU_OK with nothing written.  BLU_ERROR_OUT_OF_MEMORY if not even one work vector can be
+ * allocated (the handle stays usable), BLU_ERROR_DEVICE.
+ * Device memory: the handle keeps one work vector of m + 2 doubles, rounded up to a multiple of 32, per right-hand side in
+ * flight, and with host inputs a staging block of the same shape (one upload and one download per chunk); the two
+ * together stay within 1 GiB: more right-hand sides than that holds are worked in chunks, launched back to back with one
+ * synchronize at the end (halved further if the allocation fails).  Freed with the handle. */
+int blu_hip_solve_dense_multi(blu_hip *h, int64_t nrhs, const double *rhs, int64_t ldrhs, double *lhs, int64_t ldlhs,
+                              char trans, int inputs_on_device);
+
 /* Batch extension: blu_hip_solve_for_update and blu_hip_update for n handles on one device in one call.  Member k gets
  * exactly what blu_hip_solve_for_update(h[k], nzrhs[k], irhs[k], xrhs[k], &nzlhs[k], ilhs[k], lhs[k], trans) /
  * blu_hip_update(h[k], xtbl[k]) gives: status, pattern in the same order, the bits of the values, every statistic and
@@ -261,7 +282,8 @@ int blu_hip_update_batch(blu_hip **h, int n, const double *xtbl, int *status);
  * and the other members run regardless: BLU_ERROR_INVALID_CALL without a valid factorization,
  * BLU_ERROR_INVALID_ARGUMENT for nzrhs[k] < 0, nzrhs[k] > m or an index out of range, BLU_OK with nzlhs[k] = 0 for
  * m == 0, BLU_ERROR_OUT_OF_MEMORY, BLU_ERROR_DEVICE.  status may be NULL.  Returns the most negative member status,
- * else the largest.  Several right-hand sides for ONE handle need one call each: a handle has one workspace. */
+ * else the largest.  Several SPARSE right-hand sides for ONE handle need one call each: a handle has one sparse
+ * workspace (dense right-hand sides: blu_hip_solve_dense_multi). */
 int blu_hip_solve_sparse_batch(blu_hip **h, int n, const int64_t *nzrhs, const uint64_t *const *irhs,
                                const double *const *xrhs, int64_t *nzlhs, int64_t *const *ilhs, double *const *lhs,
                                char trans, int *status);

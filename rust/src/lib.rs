@@ -60,6 +60,9 @@ extern "C" {
         u_colptr: *mut i64, u_rowidx: *mut i64, u_value: *mut f64,
     ) -> c_int;
     fn blu_hip_solve_dense(h: *mut BluHip, rhs: *const f64, lhs: *mut f64, trans: c_char) -> c_int;
+    fn blu_hip_solve_dense_multi(
+        h: *mut BluHip, nrhs: i64, rhs: *const f64, ldrhs: i64, lhs: *mut f64, ldlhs: i64, trans: c_char, inputs_on_device: c_int,
+    ) -> c_int;
     fn blu_hip_solve_sparse(
         h: *mut BluHip, nzrhs: i64, irhs: *const u64, xrhs: *const f64, p_nzlhs: *mut i64, ilhs: *mut i64, lhs: *mut f64, trans: c_char,
     ) -> c_int;
@@ -307,6 +310,21 @@ impl BLU {
             return Err(Status::ErrorInvalidArgument);
         }
         status_of(unsafe { blu_hip_solve_dense(self.lu.h, rhs.as_ptr(), lhs.as_mut_ptr(), trans as c_char) })
+    }
+
+    /// `solve_dense` for `nrhs` right-hand sides in one call (no reference counterpart): right-hand side `j` is
+    /// `rhs[j * ldrhs..j * ldrhs + m]`, its solution goes to `lhs[j * ldlhs..j * ldlhs + m]`, each bit-identical to
+    /// `solve_dense` on the same right-hand side; what lies between `m` and a leading dimension is left alone.
+    pub fn solve_dense_multi(&mut self, nrhs: usize, rhs: &[f64], ldrhs: usize, lhs: &mut [f64], ldlhs: usize, trans: char) -> Result<(), Status> {
+        if nrhs > 1 && (ldrhs < self.m || ldlhs < self.m) {
+            return Err(Status::ErrorInvalidArgument);
+        }
+        if nrhs > 0 && (rhs.len() < (nrhs - 1) * ldrhs + self.m || lhs.len() < (nrhs - 1) * ldlhs + self.m) {
+            return Err(Status::ErrorInvalidArgument);
+        }
+        status_of(unsafe {
+            blu_hip_solve_dense_multi(self.lu.h, nrhs as i64, rhs.as_ptr(), ldrhs as i64, lhs.as_mut_ptr(), ldlhs as i64, trans as c_char, 0)
+        })
     }
 
     // lu_clear_lhs, blu.rs:380-395

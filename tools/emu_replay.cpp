@@ -17,6 +17,9 @@
 //   OP_FORUPD   trans nzrhs irhs[nzrhs] has_x xrhs[nzrhs if has_x] want status [nzlhs ilhs[nzlhs] lhs[m] if want and status == 0]
 //   OP_UPDATE   xtbl(double) status
 //   OP_STAT     key value(double)
+//   OP_MULTI_WS bytes                                       blu_hip_dbg_set_multi_ws_bytes(bytes): chunking of the next record
+//   OP_DENSE_MULTI trans nrhs ldrhs ldlhs rhs[nrhs * m] status lhs[nrhs * m]      blu_hip_solve_dense_multi with host blocks of
+//               those leading dimensions, built here: NaN between m and ldrhs, and the lhs block ends with the last solution
 //   OP_END
 #include "../include/blu_hip.h"
 
@@ -27,11 +30,13 @@
 
 // the one debug hook of the library the update tapes need (blu_update.inc); not part of the product ABI
 extern "C" int blu_hip_dbg_set_upd_extra(blu_hip *h, int64_t extra);
+// ... and the one that sets the chunking of blu_hip_solve_dense_multi (blu_solve_multi.inc)
+extern "C" int blu_hip_dbg_set_multi_ws_bytes(blu_hip *h, int64_t bytes);
 
-enum { OP_END = 0, OP_NEW, OP_EXTRA, OP_PARAM, OP_FACT, OP_DENSE, OP_SPARSE, OP_FORUPD, OP_UPDATE, OP_STAT };
+enum { OP_END = 0, OP_NEW, OP_EXTRA, OP_PARAM, OP_FACT, OP_DENSE, OP_SPARSE, OP_FORUPD, OP_UPDATE, OP_STAT, OP_MULTI_WS, OP_DENSE_MULTI };
 static const int64_t TAPE_MAGIC = 0x3145504154554c42LL; // "BLUTAPE1"
 static const char *const OP_NAME[] = {"end", "new", "dbg_set_upd_extra", "set_param", "factorize", "solve_dense", "solve_sparse",
-                                      "solve_for_update", "update", "get_stat"};
+                                      "solve_for_update", "update", "get_stat", "dbg_set_multi_ws_bytes", "solve_dense_multi"};
 
 static std::vector<int64_t> tape;
 static size_t pos = 0;
@@ -116,7 +121,7 @@ int main(int argc, char **argv)
     int64_t m = 0;
     for (;;) {
         op = word();
-        if (op < OP_END || op > OP_STAT) {
+        if (op < OP_END || op > OP_DENSE_MULTI) {
             fprintf(stderr, "emu_replay: unknown record %lld after call %ld\n", (long long)op, ncall);
             return 2;
         }
@@ -185,6 +190,28 @@ int main(int argc, char **argv)
         case OP_UPDATE: {
             const double xtbl = real();
             same_int("status", blu_hip_update(h, xtbl), word());
+            break;
+        }
+        case OP_MULTI_WS:
+            same_int("status", blu_hip_dbg_set_multi_ws_bytes(h, word()), BLU_OK);
+            break;
+        case OP_DENSE_MULTI: {
+            const char trans = (char)word();
+            const size_t nrhs = (size_t)word(), ldr = (size_t)word(), ldl = (size_t)word(), M = (size_t)m;
+            const double *rhs = (const double *)take(nrhs * M);
+            // (exactly as long as the entry may touch: an access behind the last column is an AddressSanitizer report)
+            std::vector<double> R(nrhs ? (nrhs - 1) * ldr + M : 0, __builtin_nan("")), X(nrhs ? (nrhs - 1) * ldl + M : 0, -7.25e300); // (= untouched)
+            for (size_t j = 0; j < nrhs; j++) memcpy(R.data() + j * ldr, rhs + j * M, M * 8);
+            const double untouched = -7.25e300;
+            const int st = blu_hip_solve_dense_multi(h, (int64_t)nrhs, R.data(), (int64_t)ldr, X.data(), (int64_t)ldl, trans, 0);
+            same_int("status", st, word());
+            if (st != BLU_OK) break;
+            const int64_t *want = take(nrhs * M);
+            for (size_t j = 0; j < nrhs; j++) {
+                same_words("lhs", X.data() + j * ldl, want + j * M, M, true);
+                for (size_t k = M; k < ldl && j + 1 < nrhs; k++)
+                    if (X[j * ldl + k] != untouched) differ("padding of lhs", (long)(j * ldl + k), &X[j * ldl + k], &untouched, true);
+            }
             break;
         }
         case OP_STAT: {
