@@ -10,6 +10,8 @@ with the same method names, argument meaning and error behaviour:
     .get_factors()                                 BLU::get_factors         blu.rs:139
     .solve_dense(rhs, trans)                       BLU::solve_dense         blu.rs:182
     .solve_dense_multi(rhs, trans)                 solve_dense for many right-hand sides on one handle in one call
+    .solve_sparse_multi(irhs_list, xrhs_list)      solve_sparse for many right-hand sides on one handle in one call
+    .get_sparse_multi(total)                       the compressed solutions the last solve_sparse_multi left in the handle
     solve_dense_batch(handles, rhs, trans)         solve_dense for many handles in one call (batch extension)
     solve_for_update_batch(handles, irhs, xrhs)    solve_for_update for many handles in one call (batch extension)
     update_batch(handles, xtbl)                    update for many handles in one call (batch extension)
@@ -44,6 +46,7 @@ EXPORTS = [
     "blu_hip_solve_sparse", "blu_hip_solve_for_update", "blu_hip_update", "blu_hip_set_skip_stats", "blu_hip_gen_lp_basis",
     "blu_hip_solve_dense_batch", "blu_hip_solve_for_update_batch", "blu_hip_update_batch",
     "blu_hip_solve_sparse_batch", "blu_hip_solve_dense_multi",
+    "blu_hip_solve_sparse_multi", "blu_hip_get_sparse_multi",
 ]
 
 
@@ -466,6 +469,50 @@ class BLU:
             raise BluError(st, self.last_error())
         return st
 
+    def solve_sparse_multi(self, irhs_list, xrhs_list, trans="N"):
+        """solve_sparse for many sparse right-hand sides on this handle in one call (one wave per right-hand side with a
+        workspace of its own, the factors shared; per right-hand side the status, pattern order, values and flop counters of
+        solve_sparse, bit for bit).
+
+        irhs_list[j] / xrhs_list[j]: right-hand side j.  Returns (statuses, solutions) with solutions[j] = (ilhs_j, xlhs_j):
+        the pattern in the reference's order and the values at those indices (empty for a right-hand side that was refused
+        with ERROR_INVALID_ARGUMENT).  self.lhs / self.ilhs / self.nzlhs are not touched.  A call refused as a whole,
+        ERROR_DEVICE or ERROR_OUT_OF_MEMORY raise BluError."""
+        n = len(irhs_list)
+        if len(xrhs_list) != n:
+            raise ValueError("solve_sparse_multi: one xrhs per irhs")
+        irs = [np.ascontiguousarray(a, dtype=np.uint64) for a in irhs_list]
+        xrs = [np.ascontiguousarray(a, dtype=np.float64) for a in xrhs_list]
+        for j in range(n):
+            if irs[j].shape != xrs[j].shape or irs[j].ndim != 1:
+                raise ValueError("solve_sparse_multi: right-hand side %d: irhs and xrhs need equal lengths" % j)
+        ptr = np.zeros(n + 1, np.int64)
+        ptr[1:] = np.cumsum([len(a) for a in irs])
+        ir = np.concatenate(irs) if n else np.zeros(0, np.uint64)
+        xr = np.concatenate(xrs) if n else np.zeros(0)
+        lp = np.zeros(n + 1, np.int64)
+        st = np.zeros(max(n, 1), np.int32)
+        L = lib()
+        L.blu_hip_solve_sparse_multi.argtypes = [C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_char, C.c_void_p, C.c_void_p]
+        rc = L.blu_hip_solve_sparse_multi(self._h, n, ptr.ctypes.data, ir.ctypes.data if len(ir) else None, xr.ctypes.data if len(xr) else None,
+                                          trans.encode()[0:1], lp.ctypes.data, st.ctypes.data)
+        sts = [int(s) for s in st[:n]]
+        if rc < 0 and (rc in (K.ERROR_DEVICE, K.ERROR_OUT_OF_MEMORY) or not any(s == rc for s in sts)):
+            raise BluError(rc, self.last_error())
+        il, xl = self.get_sparse_multi(int(lp[n]))
+        return sts, [(il[lp[j]:lp[j + 1]], xl[lp[j]:lp[j + 1]]) for j in range(n)]
+
+    def get_sparse_multi(self, total):
+        """The compressed solutions of the last solve_sparse_multi: (ilhs, xlhs) of `total` = lhs_ptr[nrhs] entries each.
+        May be called any number of times; raises BluError(ERROR_INVALID_CALL) if no result is held."""
+        il, xl = np.zeros(total, np.int64), np.zeros(total)
+        L = lib()
+        L.blu_hip_get_sparse_multi.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p]
+        st = L.blu_hip_get_sparse_multi(self._h, il.ctypes.data if total else None, xl.ctypes.data if total else None)
+        if st != K.OK:
+            raise BluError(st, self.last_error())
+        return il, xl
+
     def _clear_lhs(self):
         m = self.m
         if self.lhs is None:
@@ -537,6 +584,18 @@ class BLU:
         lib().blu_hip_dbg_multi_last_chunk.restype = C.c_int64
         lib().blu_hip_dbg_multi_last_chunk.argtypes = [C.c_void_p]
         return int(lib().blu_hip_dbg_multi_last_chunk(self._h))
+
+    def dbg_set_sparse_multi_ws_bytes(self, n):
+        """Byte limit of the workspace pool of solve_sparse_multi (-1: the default, 1 GiB; a slot takes 48 m + 64 bytes);
+        small values force the chunking at small shapes."""
+        lib().blu_hip_dbg_set_sparse_multi_ws_bytes.argtypes = [C.c_void_p, C.c_int64]
+        lib().blu_hip_dbg_set_sparse_multi_ws_bytes(self._h, int(n))
+
+    def dbg_sparse_multi_last_chunk(self):
+        """Right-hand sides per chunk of the last solve_sparse_multi."""
+        lib().blu_hip_dbg_sparse_multi_last_chunk.restype = C.c_int64
+        lib().blu_hip_dbg_sparse_multi_last_chunk.argtypes = [C.c_void_p]
+        return int(lib().blu_hip_dbg_sparse_multi_last_chunk(self._h))
 
     def dbg_set_grid_blocks(self, n):
         """Workgroups of the chip-wide O(nnz) phases of a single factorize (1 = one workgroup, as inside a batch)."""

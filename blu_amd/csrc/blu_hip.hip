@@ -97,6 +97,21 @@ struct blu_hip {
     int64_t mws_cols, mio_cols;  // columns (of multi_stride doubles) they hold
     int64_t multi_ws_bytes;      // debug: byte limit of the two together (-1: default)
     int64_t multi_last_chunk;    // columns per chunk of the last call
+    // blu_hip_solve_sparse_multi (blu_solve_sparse_multi.inc): the pool of per-solve workspaces, its staging and result buffers
+    // on the device, and the result of the last call on the host
+    SparseSlots sm_pool;
+    int64_t sm_slots;            // slots the pool holds (0: none)
+    int sm_marker;               // the pool's own marker: 0 <= marked <= sm_marker in every slot
+    char *sm_stage;              // packed right-hand sides of one chunk
+    size_t sm_stage_cap;
+    int *sm_gidx;                // gathered solutions of the call
+    double *sm_gval;
+    int64_t sm_gcap;
+    int64_t sm_ws_bytes;         // debug: byte limit of the pool (-1: default)
+    int64_t sm_last_chunk;       // right-hand sides per chunk of the last call
+    bool sm_have;                // a result is held
+    std::vector<int64_t> sm_ilhs;
+    std::vector<double> sm_xlhs;
     int64_t sp_l_flops, sp_u_flops; // lu.l_flops / lu.u_flops
     int sp_branch;                  // 1 sparse, 2 sequential: branch of the last solve_sparse (diagnostic)
     // timing
@@ -165,6 +180,7 @@ static const int64_t kIntMax = 0x7ffffff0;
 
 static void free_upd(blu_hip *h);
 static void free_multi(blu_hip *h);
+static void free_sparse_multi(blu_hip *h);
 static void free_all(blu_hip *h)
 {
     DevLU &D = h->D;
@@ -182,6 +198,7 @@ static void free_all(blu_hip *h)
     dfree(h->ur_len); dfree(h->ur_pos); dfree(h->ur_val);
     free_upd(h);
     free_multi(h);
+    free_sparse_multi(h);
     // everything else lives in the slab
     dfree(h->slab);
 }
@@ -270,6 +287,17 @@ extern "C" blu_hip *blu_hip_new(int64_t m, int64_t b_nz, int device)
     h->mws_cols = h->mio_cols = 0;
     h->multi_ws_bytes = -1;
     h->multi_last_chunk = 0;
+    memset(&h->sm_pool, 0, sizeof(SparseSlots));
+    h->sm_slots = 0;
+    h->sm_marker = 0;
+    h->sm_stage = nullptr;
+    h->sm_stage_cap = 0;
+    h->sm_gidx = nullptr;
+    h->sm_gval = nullptr;
+    h->sm_gcap = 0;
+    h->sm_ws_bytes = -1;
+    h->sm_last_chunk = 0;
+    h->sm_have = false;
     h->chain_ok = 0;
     h->chain_defects = 0;
     h->ur_len = h->ur_pos = nullptr;
@@ -908,6 +936,7 @@ extern "C" int blu_hip_solve_dense(blu_hip *h, const double *rhs, double *lhs, c
 #include "blu_solve_multi.inc"
 #include "blu_update_batch.inc"
 #include "blu_solve_sparse_batch.inc"
+#include "blu_solve_sparse_multi.inc"
 
 // solve_sparse -- src/solve_sparse.rs:36-68, lu/solve_sparse.rs:11-360 (fresh factorization: nforrest == 0)
 extern "C" int blu_hip_solve_sparse(blu_hip *h, int64_t nzrhs, const uint64_t *irhs, const double *xrhs, int64_t *p_nzlhs,

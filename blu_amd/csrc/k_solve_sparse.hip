@@ -591,3 +591,89 @@ __global__ void __launch_bounds__(1024) k_build_lt_batch(const DevLU *Ds, const 
     const SparseWs &W = Ws[blockIdx.x];
     build_lt_body(DevG(Ds[blockIdx.x]), W.lt_ptr, W.lt_idx, W.lt_val, W.lt_cur, &carry, part);
 }
+
+// ---------------------------------------------------------------------------------------------------------
+// blu_hip_solve_sparse_multi: n sparse right-hand sides on ONE factorization, one wave each.  What a solve writes is
+// its SparseWs alone (marks, DFS stacks, work vectors, output pattern); the factors and the row-wise L are only read.
+// The handle keeps a pool of such workspaces: slot s owns the elements [s*m, (s+1)*m) of each array below and
+// out[8*s .. 8*s + 5), with the invariants of the handle's own workspace (work / xlhs all zero between launches,
+// 0 <= marked <= the pool's marker).
+// ---------------------------------------------------------------------------------------------------------
+struct SparseSlots {
+    int *marked, *psym, *pat, *pstack, *estack, *ilhs;
+    double *work, *xlhs, *xval;
+    long long *out;
+    long long m;
+};
+// the right-hand sides of one chunk, packed: column s is irhs / xrhs[beg[s] .. beg[s] + cnt[s]); cnt[s] < 0 marks a
+// column the host refused (it keeps its slot, with an empty solution)
+struct MultiRhs {
+    const long long *beg;
+    const int *cnt;
+    const int *irhs;
+    const double *xrhs;
+};
+// slot s as a SparseWs; the row-wise L is the handle's (H), shared by every slot
+__device__ __forceinline__ SparseWs slot_ws(const SparseSlots &P, const SparseWs &H, long long s)
+{
+    const long long o = s * P.m;
+    SparseWs W = H;
+    W.marked = P.marked + o;
+    W.psym = P.psym + o;
+    W.pat = P.pat + o;
+    W.pstack = P.pstack + o;
+    W.estack = P.estack + o;
+    W.work = P.work + o;
+    W.xlhs = P.xlhs + o;
+    W.ilhs = P.ilhs + o;
+    W.xval = P.xval + o;
+    W.out = P.out + 8 * s;
+    return W;
+}
+// true: column s was refused by the host; its counters are zeroed and the wave is done
+__device__ __forceinline__ bool slot_skipped(const SparseWs &W, int cnt)
+{
+    if (cnt >= 0) return false;
+    if (lane_id() == 0)
+        for (int q = 0; q < 5; q++) W.out[q] = 0;
+    return true;
+}
+// fresh factorization: the body of k_solve_sparse with the handle's one DevLU / FinishOut and slot blockIdx.x
+__global__ void __launch_bounds__(64) k_solve_sparse_multi(const DevLU *Ds, const FinishOut *Os, SparseSlots P, SparseWs H, MultiRhs R, int trans,
+                                                           int marker, int nz_sparse)
+{
+    __shared__ DfsRing dfs_ring;
+    const long long s = blockIdx.x;
+    const SparseWs W = slot_ws(P, H, s);
+    const int cnt = R.cnt[s];
+    if (slot_skipped(W, cnt)) return;
+    const long long b = R.beg[s];
+    solve_sparse_wave(DevG(Ds[0]), Os[0], W, cnt, R.irhs + b, R.xrhs + b, trans, marker, nz_sparse, &dfs_ring);
+    if (lane_id() == 0) W.out[4] = 0; // (no row etas)
+}
+
+// the compressed solutions of the slots of one chunk into the result buffer of the call, behind the `base` entries of
+// the chunks before it: slot b's out[0] entries of ilhs / xval go to base + (sum of out[0] over the slots in front).
+// Each workgroup sums the counters in front of its slot itself (at most 8192 slots a chunk, blu_solve_sparse_multi.inc),
+// so that the host uploads nothing between the solves and the gather.
+__global__ void __launch_bounds__(256) k_gather_lhs_multi(SparseSlots P, long long base, int *gidx, double *gval)
+{
+    __shared__ long long part[256];
+    const int b = blockIdx.x, tid = threadIdx.x;
+    long long sum = 0;
+    for (int s = tid; s < b; s += 256) sum += P.out[8 * (long long)s];
+    part[tid] = sum;
+    __syncthreads();
+    for (int o = 128; o > 0; o >>= 1) {
+        if (tid < o) part[tid] += part[tid + o];
+        __syncthreads();
+    }
+    const long long o = base + part[0];
+    const int nz = (int)P.out[8 * (long long)b];
+    const int *il = P.ilhs + (long long)b * P.m;
+    const double *xv = P.xval + (long long)b * P.m;
+    for (int n = tid; n < nz; n += 256) {
+        gidx[o + n] = il[n];
+        gval[o + n] = xv[n];
+    }
+}

@@ -225,6 +225,10 @@ __device__ __forceinline__ void garbage_perm_wave(const UpdWs &U, int m, int *ma
 // k_solve_upd: solve_sparse on an updated factorization (mode 0) and solve_for_update (mode 1), both systems.
 // out[0] nz of the solution, [1] l_flops, [2] u_flops, [3] branch (1 sparse, 2 sequential), [4] r_flops
 // ---------------------------------------------------------------------------------------------------------
+// OWN_STATE = false (mode 0 only, k_solve_upd_multi): many waves run the body on ONE UpdWs.  In mode 0 it only reads
+// the U files, the etas and the pivot sequence; the two writes to the shared UpdState -- the status at the top, the flop
+// counters at the end -- are left out, the counters stay in W.out[1..4] and are added once behind the waves.
+template <bool OWN_STATE = true>
 __device__ __forceinline__ void solve_upd_wave(const DevG &D, const SparseWs &W, const UpdWs &U, int mode, int want_solution, int nrhs,
                                                const int *irhs, const double *xrhs, int trans, int marker, int nz_sparse, DfsRing *ring)
 {
@@ -240,7 +244,7 @@ __device__ __forceinline__ void solve_upd_wave(const DevG &D, const SparseWs &W,
     const GraphUc GU{U.ucbeg, U.uclen, U.ucidx, U.ucval, U.row_pivot};
     const GraphL GL{D.pinv, D.lbeg, D.lidx, D.lval};
     const GraphLt GT{W.lt_ptr, W.lt_idx, W.lt_val};
-    if (lane == 0) st->status = UPD_OK;
+    if (OWN_STATE && lane == 0) st->status = UPD_OK;
     bool have_solution = true;
 
     if (trans) {
@@ -499,10 +503,12 @@ __device__ __forceinline__ void solve_upd_wave(const DevG &D, const SparseWs &W,
         W.out[2] = u_flops;
         W.out[3] = branch;
         W.out[4] = r_flops;
-        st->l_flops += l_flops;
-        st->u_flops += u_flops;
-        st->r_flops += r_flops;
-        st->update_cost_numer += (double)r_flops;
+        if (OWN_STATE) {
+            st->l_flops += l_flops;
+            st->u_flops += u_flops;
+            st->r_flops += r_flops;
+            st->update_cost_numer += (double)r_flops;
+        }
     }
 }
 __global__ void __launch_bounds__(64) k_solve_upd(DevLU *Ds, SparseWs W, UpdWs U, int mode, int want_solution, int nrhs, const int *irhs,
@@ -1193,4 +1199,33 @@ __global__ void __launch_bounds__(64) k_solve_dense_upd_multi(const DevLU *__res
     const long long j = blockIdx.x;
     U.work1 = ws + j * wstride;
     solve_dense_upd_wave(DevG(Ds[0]), W, U, rhs + j * ldrhs, lhs + j * ldlhs, trans, marker);
+}
+
+// ---------------------------------------------------------------------------------------------------------
+// blu_hip_solve_sparse_multi on an updated factorization: n sparse right-hand sides on ONE handle, one wave each, slot
+// blockIdx.x of the pool (k_solve_sparse.hip) as its SparseWs and the handle's one UpdWs, which mode 0 only reads
+// (solve_upd_wave<false>).  k_upd_add_flops then leaves the shared UpdState as the n single calls would have: status
+// UPD_OK and the counters grown by the sums the host took from the slots (integer counts: the order does not matter).
+// ---------------------------------------------------------------------------------------------------------
+__global__ void __launch_bounds__(64) k_solve_upd_multi(const DevLU *Ds, SparseSlots P, SparseWs H, UpdWs U, MultiRhs R, int trans, int marker,
+                                                        int nz_sparse)
+{
+    __shared__ DfsRing dfs_ring;
+    const long long s = blockIdx.x;
+    const SparseWs W = slot_ws(P, H, s);
+    const int cnt = R.cnt[s];
+    if (slot_skipped(W, cnt)) return;
+    const long long b = R.beg[s];
+    solve_upd_wave<false>(DevG(Ds[0]), W, U, 0, 1, cnt, R.irhs + b, R.xrhs + b, trans, marker, nz_sparse, &dfs_ring);
+}
+__global__ void __launch_bounds__(64) k_upd_add_flops(UpdWs U, long long l_flops, long long u_flops, long long r_flops)
+{
+    if (threadIdx.x == 0) {
+        UpdState *st = U.st;
+        st->status = UPD_OK;
+        st->l_flops += l_flops;
+        st->u_flops += u_flops;
+        st->r_flops += r_flops;
+        st->update_cost_numer += (double)r_flops;
+    }
 }

@@ -282,11 +282,61 @@ int blu_hip_update_batch(blu_hip **h, int n, const double *xtbl, int *status);
  * and the other members run regardless: BLU_ERROR_INVALID_CALL without a valid factorization,
  * BLU_ERROR_INVALID_ARGUMENT for nzrhs[k] < 0, nzrhs[k] > m or an index out of range, BLU_OK with nzlhs[k] = 0 for
  * m == 0, BLU_ERROR_OUT_OF_MEMORY, BLU_ERROR_DEVICE.  status may be NULL.  Returns the most negative member status,
- * else the largest.  Several SPARSE right-hand sides for ONE handle need one call each: a handle has one sparse
- * workspace (dense right-hand sides: blu_hip_solve_dense_multi). */
+ * else the largest.  Several SPARSE right-hand sides for ONE handle: blu_hip_solve_sparse_multi below (dense ones:
+ * blu_hip_solve_dense_multi). */
 int blu_hip_solve_sparse_batch(blu_hip **h, int n, const int64_t *nzrhs, const uint64_t *const *irhs,
                                const double *const *xrhs, int64_t *nzlhs, int64_t *const *ilhs, double *const *lhs,
                                char trans, int *status);
+
+/* Several SPARSE right-hand sides on ONE handle: blu_hip_solve_sparse for nrhs right-hand sides in one call.  Right-hand
+ * side j is irhs / xrhs[rhs_ptr[j] .. rhs_ptr[j+1]) (compressed columns: rhs_ptr has nrhs + 1 non-decreasing entries, no
+ * index twice inside a column).  Right-hand side j gets exactly what blu_hip_solve_sparse(h, nz_j, irhs_j, xrhs_j, ...,
+ * trans) gives on the same handle: status, number of nonzeros, the pattern in the reference's order and the bits of
+ * the values -- on fresh (rank-deficient included) and on updated factorizations, both systems, and on both branches of
+ * the second triangular solve, chosen per right-hand side by BLU_PARAM_SPARSE_THRES.
+ * The call writes lhs_ptr[0 .. nrhs]: lhs_ptr[0] = 0, solution j has lhs_ptr[j+1] - lhs_ptr[j] nonzeros.  The compressed
+ * solutions stay in the handle (on the host) until the next blu_hip_solve_sparse_multi or blu_hip_free;
+ * blu_hip_get_sparse_multi copies them into ilhs / xlhs of lhs_ptr[nrhs] entries each, any number of times: solution j
+ * in [lhs_ptr[j], lhs_ptr[j+1]), the indices blu_hip_solve_sparse leaves in ilhs[0 .. nzlhs) and the values lhs[ilhs[n]].
+ * No capacity has to be guessed and no solve is ever repeated because a buffer was too small.
+ * status may be NULL; status[j] is BLU_OK, or BLU_ERROR_INVALID_ARGUMENT for a column of more than m entries or with an
+ * index out of range: that column gets an empty solution and counts nothing, the others are solved regardless.  Returns
+ * the most negative status, else the largest.
+ * Checked in this order, and a call refused as a whole touches nothing (lhs_ptr, status, the held result, the counters,
+ * the handle): NULL h BLU_ERROR_ARGUMENT_MISSING; no valid factorization BLU_ERROR_INVALID_CALL; NULL rhs_ptr or lhs_ptr
+ * BLU_ERROR_ARGUMENT_MISSING; NULL irhs or xrhs while rhs_ptr[nrhs] > rhs_ptr[0] BLU_ERROR_ARGUMENT_MISSING; nrhs < 0, a
+ * negative rhs_ptr[0] or a decreasing rhs_ptr BLU_ERROR_INVALID_ARGUMENT; nrhs == 0 BLU_OK with an empty result held;
+ * m == 0 every solution empty.  Failures of the call itself come after these checks and fail it as a whole, with
+ * lhs_ptr, status, the counters and the result held before left as they were: BLU_ERROR_OUT_OF_MEMORY if not even one
+ * workspace, the staging block or the result buffer can be allocated (the handle stays usable), BLU_ERROR_DEVICE for a
+ * failed HIP call.  The solves on updated factors cannot ask for storage or meet a broken invariant in this mode and do
+ * not write the shared status word, so no right-hand side can report such a state on its own: the one impossible state
+ * the host can see, a solution count outside 0 .. m, is BLU_ERROR_DEVICE for the WHOLE call (the workspaces are dropped
+ * and allocated again by the next call), not for that right-hand side alone.
+ * Afterwards the handle is as after the nrhs single calls in order, wherever that can be observed: BLU_STAT_L_FLOPS,
+ * U_FLOPS, R_FLOPS and BLU_STAT_UPDATE_COST have grown by the sums over the solved right-hand sides (added once, behind
+ * the waves), the branch statistic is that of the last solved one, the row-wise L a transposed call built is kept, a
+ * pending blu_hip_solve_for_update (spike, row eta) is untouched -- a multi call between the two solve_for_update calls
+ * and blu_hip_update leaves the update exactly as it would have been --, the handle's own sparse workspace is not
+ * touched and later calls continue with the bits they would have had.
+ * Each right-hand side runs on ONE wave with a workspace of its own, the factors shared (k_solve_sparse_multi; after
+ * updates k_solve_upd_multi, which reads the mutable U, the etas and the pivot sequence and leaves the shared update
+ * state to k_upd_add_flops, one lane, once).  The kernels keep 24 KB of LDS per wave, so about 6 per CU run at once and
+ * the rest follow inside the same launch.
+ * Device memory: the handle keeps a pool of workspaces, 48 bytes per row plus 64 bytes each, within 1 GiB and at most
+ * 8192 of them; more right-hand sides are worked in chunks, one after the other (halved further if the allocation
+ * fails).  The pool has a marker of its own.  Freed with the handle.
+ * Cost, per chunk: one upload (all its right-hand sides, packed; the workspaces are addressed by slot number, so there
+ * are no descriptors to send), one solve launch, one synchronize, one download of the counters, one gather launch
+ * (k_gather_lhs_multi).  The counters size the result buffer, so the host waits for a chunk's solves before it starts
+ * the next chunk: chunks run one after the other, not back to back.  For the call: one synchronize and the download of the gathered solutions (indices and values,
+ * one copy each), and the one-off k_build_lt when a transposed call on a fresh handle lacks the row-wise L.  Nothing is
+ * copied or synchronized per right-hand side. */
+int blu_hip_solve_sparse_multi(blu_hip *h, int64_t nrhs, const int64_t *rhs_ptr, const uint64_t *irhs, const double *xrhs,
+                               char trans, int64_t *lhs_ptr, int *status);
+/* BLU_ERROR_INVALID_CALL if no result of blu_hip_solve_sparse_multi is held; BLU_ERROR_ARGUMENT_MISSING for a NULL handle,
+ * or for NULL arrays while the held total is above 0. */
+int blu_hip_get_sparse_multi(blu_hip *h, int64_t *ilhs, double *xlhs);
 
 /* factorize() ends with the statistics tail of src/factorize.rs:121-147 (condest(L), condest(U),
  * residual_test; getters BLU_STAT_CONDEST_* .. BLU_STAT_RESIDUAL_TEST).  It is a chain of 8 triangular

@@ -79,6 +79,11 @@ extern "C" {
         h: *mut *mut BluHip, n: c_int, nzrhs: *const i64, irhs: *const *const u64, xrhs: *const *const f64, nzlhs: *mut i64,
         ilhs: *const *mut i64, lhs: *const *mut f64, trans: c_char, status: *mut c_int,
     ) -> c_int;
+    fn blu_hip_solve_sparse_multi(
+        h: *mut BluHip, nrhs: i64, rhs_ptr: *const i64, irhs: *const u64, xrhs: *const f64, trans: c_char, lhs_ptr: *mut i64,
+        status: *mut c_int,
+    ) -> c_int;
+    fn blu_hip_get_sparse_multi(h: *mut BluHip, ilhs: *mut i64, xlhs: *mut f64) -> c_int;
     fn blu_hip_last_error(h: *const BluHip) -> *const c_char;
 }
 
@@ -325,6 +330,51 @@ impl BLU {
         status_of(unsafe {
             blu_hip_solve_dense_multi(self.lu.h, nrhs as i64, rhs.as_ptr(), ldrhs as i64, lhs.as_mut_ptr(), ldlhs as i64, trans as c_char, 0)
         })
+    }
+
+    /// `solve_sparse` for `rhs_ptr.len() - 1` sparse right-hand sides in one call (no reference counterpart): right-hand
+    /// side `j` is `irhs[rhs_ptr[j]..rhs_ptr[j + 1]]` / `xrhs[..]` (compressed columns).  Returns per right-hand side its
+    /// status, and the compressed solutions `(lhs_ptr, ilhs, xlhs)`: solution `j` is `ilhs[lhs_ptr[j]..lhs_ptr[j + 1]]` in
+    /// the reference's pattern order with its values, each bit-identical to `solve_sparse` on the same right-hand side.
+    /// `self.lhs` / `self.ilhs` / `self.nzlhs` are not touched.  A call refused as a whole, a device failure or an
+    /// allocation failure is the outer `Err`.
+    #[allow(clippy::type_complexity)]
+    pub fn solve_sparse_multi(
+        &mut self, rhs_ptr: &[usize], irhs: &[usize], xrhs: &[f64], trans: char,
+    ) -> Result<(Vec<Result<(), Status>>, Vec<usize>, Vec<usize>, Vec<f64>), Status> {
+        // the C side reads rhs_ptr[0..=nrhs] and irhs / xrhs[rhs_ptr[0]..rhs_ptr[nrhs]): never hand it offsets beyond the slices
+        if rhs_ptr.is_empty() || rhs_ptr.windows(2).any(|w| w[1] < w[0]) {
+            return Err(Status::ErrorInvalidArgument);
+        }
+        let nrhs = rhs_ptr.len() - 1;
+        if rhs_ptr[nrhs] > irhs.len() || rhs_ptr[nrhs] > xrhs.len() {
+            return Err(Status::ErrorInvalidArgument);
+        }
+        let ptr: Vec<i64> = rhs_ptr.iter().map(|&p| p as i64).collect();
+        let mut lhs_ptr = vec![0i64; nrhs + 1];
+        let mut status = vec![-99 as c_int; nrhs.max(1)];
+        let code = unsafe {
+            blu_hip_solve_sparse_multi(
+                self.lu.h, nrhs as i64, ptr.as_ptr(), irhs.as_ptr() as *const u64, xrhs.as_ptr(), trans as c_char, lhs_ptr.as_mut_ptr(),
+                status.as_mut_ptr(),
+            )
+        };
+        // refused as a whole (no status written), or a failure of the call itself
+        if code < 0 && (code == -9 || status[..nrhs].iter().all(|&s| s != code)) {
+            return Err(status_of(code).unwrap_err());
+        }
+        let total = lhs_ptr[nrhs] as usize;
+        let mut ilhs = vec![0i64; total];
+        let mut xlhs = vec![0f64; total];
+        if total > 0 {
+            status_of(unsafe { blu_hip_get_sparse_multi(self.lu.h, ilhs.as_mut_ptr(), xlhs.as_mut_ptr()) })?;
+        }
+        Ok((
+            status[..nrhs].iter().map(|&s| status_of(s)).collect(),
+            lhs_ptr.iter().map(|&p| p as usize).collect(),
+            ilhs.iter().map(|&i| i as usize).collect(),
+            xlhs,
+        ))
     }
 
     // lu_clear_lhs, blu.rs:380-395

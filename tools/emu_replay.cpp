@@ -20,6 +20,11 @@
 //   OP_MULTI_WS bytes                                       blu_hip_dbg_set_multi_ws_bytes(bytes): chunking of the next record
 //   OP_DENSE_MULTI trans nrhs ldrhs ldlhs rhs[nrhs * m] status lhs[nrhs * m]      blu_hip_solve_dense_multi with host blocks of
 //               those leading dimensions, built here: NaN between m and ldrhs, and the lhs block ends with the last solution
+//   OP_SPARSE_MULTI_WS bytes                                blu_hip_dbg_set_sparse_multi_ws_bytes(bytes): chunking of the next record
+//   OP_SPARSE_MULTI trans nrhs rhs_ptr[nrhs + 1] irhs[tot] xrhs[tot] rc status[nrhs] lhs_ptr[nrhs + 1] ilhs[total] xlhs[total]
+//               blu_hip_solve_sparse_multi with host arrays built here that end with their last entry (tot = rhs_ptr[nrhs],
+//               total = lhs_ptr[nrhs]; rhs_ptr[0] = 0), then blu_hip_get_sparse_multi into arrays of exactly total entries
+//   OP_SPARSE_MULTI_GET total ilhs[total] xlhs[total]       blu_hip_get_sparse_multi twice: the held result, both times
 //   OP_END
 #include "../include/blu_hip.h"
 
@@ -32,11 +37,15 @@
 extern "C" int blu_hip_dbg_set_upd_extra(blu_hip *h, int64_t extra);
 // ... and the one that sets the chunking of blu_hip_solve_dense_multi (blu_solve_multi.inc)
 extern "C" int blu_hip_dbg_set_multi_ws_bytes(blu_hip *h, int64_t bytes);
+// ... and of blu_hip_solve_sparse_multi (blu_solve_sparse_multi.inc)
+extern "C" int blu_hip_dbg_set_sparse_multi_ws_bytes(blu_hip *h, int64_t bytes);
 
-enum { OP_END = 0, OP_NEW, OP_EXTRA, OP_PARAM, OP_FACT, OP_DENSE, OP_SPARSE, OP_FORUPD, OP_UPDATE, OP_STAT, OP_MULTI_WS, OP_DENSE_MULTI };
+enum { OP_END = 0, OP_NEW, OP_EXTRA, OP_PARAM, OP_FACT, OP_DENSE, OP_SPARSE, OP_FORUPD, OP_UPDATE, OP_STAT, OP_MULTI_WS, OP_DENSE_MULTI,
+       OP_SPARSE_MULTI_WS, OP_SPARSE_MULTI, OP_SPARSE_MULTI_GET };
 static const int64_t TAPE_MAGIC = 0x3145504154554c42LL; // "BLUTAPE1"
 static const char *const OP_NAME[] = {"end", "new", "dbg_set_upd_extra", "set_param", "factorize", "solve_dense", "solve_sparse",
-                                      "solve_for_update", "update", "get_stat", "dbg_set_multi_ws_bytes", "solve_dense_multi"};
+                                      "solve_for_update", "update", "get_stat", "dbg_set_multi_ws_bytes", "solve_dense_multi",
+                                      "dbg_set_sparse_multi_ws_bytes", "solve_sparse_multi", "get_sparse_multi"};
 
 static std::vector<int64_t> tape;
 static size_t pos = 0;
@@ -121,7 +130,7 @@ int main(int argc, char **argv)
     int64_t m = 0;
     for (;;) {
         op = word();
-        if (op < OP_END || op > OP_DENSE_MULTI) {
+        if (op < OP_END || op > OP_SPARSE_MULTI_GET) {
             fprintf(stderr, "emu_replay: unknown record %lld after call %ld\n", (long long)op, ncall);
             return 2;
         }
@@ -211,6 +220,51 @@ int main(int argc, char **argv)
                 same_words("lhs", X.data() + j * ldl, want + j * M, M, true);
                 for (size_t k = M; k < ldl && j + 1 < nrhs; k++)
                     if (X[j * ldl + k] != untouched) differ("padding of lhs", (long)(j * ldl + k), &X[j * ldl + k], &untouched, true);
+            }
+            break;
+        }
+        case OP_SPARSE_MULTI_WS:
+            same_int("status", blu_hip_dbg_set_sparse_multi_ws_bytes(h, word()), BLU_OK);
+            break;
+        case OP_SPARSE_MULTI: {
+            const char trans = (char)word();
+            const size_t nrhs = (size_t)word();
+            const int64_t *p = take(nrhs + 1);
+            const size_t tot = (size_t)p[nrhs];
+            // (copies that end with their last entry: a read behind them is an AddressSanitizer report)
+            std::vector<int64_t> rhs_ptr(p, p + nrhs + 1), lhs_ptr(nrhs + 1, -1);
+            const uint64_t *ti = (const uint64_t *)take(tot);
+            std::vector<uint64_t> irhs(ti, ti + tot);
+            const double *tx = (const double *)take(tot);
+            std::vector<double> xrhs(tx, tx + tot);
+            std::vector<int> status(nrhs, -99);
+            const int rc = blu_hip_solve_sparse_multi(h, (int64_t)nrhs, rhs_ptr.data(), tot ? irhs.data() : nullptr, tot ? xrhs.data() : nullptr,
+                                                      trans, lhs_ptr.data(), status.data());
+            same_int("return value", rc, word());
+            const int64_t *ws = take(nrhs);
+            for (size_t j = 0; j < nrhs; j++)
+                if (status[j] != ws[j]) {
+                    const int64_t got = status[j];
+                    differ("status", (long)j, &got, ws + j, false);
+                }
+            same_words("lhs_ptr", lhs_ptr.data(), take(nrhs + 1), nrhs + 1, false);
+            const size_t total = (size_t)lhs_ptr[nrhs];
+            std::vector<int64_t> ilhs(total, -1); // (exactly total entries: a write behind them is an AddressSanitizer report)
+            std::vector<double> xlhs(total, 0.0);
+            same_int("get status", blu_hip_get_sparse_multi(h, total ? ilhs.data() : nullptr, total ? xlhs.data() : nullptr), BLU_OK);
+            same_words("ilhs", ilhs.data(), take(total), total, false);
+            same_words("xlhs", xlhs.data(), take(total), total, true);
+            break;
+        }
+        case OP_SPARSE_MULTI_GET: {
+            const size_t total = (size_t)word();
+            const int64_t *wi = take(total), *wx = take(total);
+            for (int rep = 0; rep < 2; rep++) {
+                std::vector<int64_t> ilhs(total, -1);
+                std::vector<double> xlhs(total, 0.0);
+                same_int("get status", blu_hip_get_sparse_multi(h, total ? ilhs.data() : nullptr, total ? xlhs.data() : nullptr), BLU_OK);
+                same_words("ilhs", ilhs.data(), wi, total, false);
+                same_words("xlhs", xlhs.data(), wx, total, true);
             }
             break;
         }
