@@ -47,7 +47,7 @@ __shared__ int g_pivot_err_line; // source line of a bounded loop that overran (
 // Diagnostic build (-DBLU_PROFILE, `make prof`): thread 0 stamps the shader clock at phase boundaries
 // of the pivot loop.  The product build contains no stamps.
 #ifdef BLU_PROFILE
-__shared__ long long g_pstamp[48];
+__shared__ long long g_pstamp[56];
 #define PROF_STAMP(k)                                                      \
     do {                                                                   \
         if (threadIdx.x == 0) g_pstamp[k] = (long long)__builtin_amdgcn_s_memtime(); \
@@ -84,8 +84,20 @@ struct alignas(16) Sm {
     };
 #ifdef BLU_PROFILE
     long long prof[48];
+    long long prof2[8];
 #else
     long long prof[1];
+#endif
+#if !BLU_CFG_WAVE
+    // runs of singleton-column pivots (scol_setup_next, k_pivot_fast.hip): the second working set, and the dispatch words
+    // of a pivot that was set up during the finalize step of its predecessor
+    Fast fb;
+    struct alignas(16) {
+        int nx_pr, nx_pc, nx_nzr, nx_where;
+    };
+    int nx_prb, nx_pcb, nx_nsr;
+    int mg; // 1: the barrier that ended the finalize step was also the barrier after the next pivot's set-up
+    long long nrun[2];
 #endif
     int rank, rankdef, min_colnz, min_rownz;
     int cused, rused, lused, uused;
@@ -1249,9 +1261,12 @@ __device__ __forceinline__ void pivot_loop_body(DevLU *Ds, int stop_at, Sm *sm, 
         sm->fa.ewValid = 0;
         sm->fa.spOk = 0;
         for (int k = 0; k < 6; k++) sm->kinds[k] = 0;
+        sm->mg = 0;
+        sm->nrun[0] = sm->nrun[1] = 0;
 #ifdef BLU_PROFILE
         for (int k = 0; k < 48; k++) sm->prof[k] = 0;
-        for (int k = 0; k < 48; k++) g_pstamp[k] = 0;
+        for (int k = 0; k < 8; k++) sm->prof2[k] = 0;
+        for (int k = 0; k < 56; k++) g_pstamp[k] = 0;
 #endif
     }
     for (int k = tid; k < (int)blockDim.x; k += blockDim.x) sm->swork[k] = 0.0; // num_waves() x 64
@@ -1266,7 +1281,90 @@ __device__ __forceinline__ void pivot_loop_body(DevLU *Ds, int stop_at, Sm *sm, 
 
     // Three workgroup barriers per pivot: wave 0 alone runs [record previous pivot -> loop head -> search
     // + set-up] while the other waves wait at the barrier below; the pivot functions hold the other two
-    // (after the line updates, after the finalize step).
+    // (after the line updates, after the finalize step).  Inside a run of singleton-column pivots there are two: wave 0
+    // sets the next pivot up during the finalize step and the loop below does not come back here (see the dispatch).
+#ifdef BLU_PROFILE
+        // a stamp of a code path that did not run in this pivot is stale (or was never written): only differences of
+        // stamps taken in order inside THIS pivot are added
+#define PROF_ADD(k, a, b)                                                                                           \
+    do {                                                                                                            \
+        const long long d_ = g_pstamp[a] - g_pstamp[b];                                                             \
+        if (g_pstamp[b] >= g_pstamp[0] && d_ >= 0 && d_ < (1LL << 28)) sm->prof[k] += d_;                            \
+    } while (0)
+#define PROF_ADD2(k, a, b)                                                                                          \
+    do {                                                                                                            \
+        const long long d_ = g_pstamp[a] - g_pstamp[b];                                                             \
+        if (g_pstamp[b] >= g_pstamp[0] && d_ >= 0 && d_ < (1LL << 28)) sm->prof2[k] += d_;                           \
+    } while (0)
+    auto prof_account = [&](int kind_done) { // thread 0, after a pivot
+        {
+            const int kk = kind_done == 1 ? 1 : (kind_done == 2 ? 2 : 3);
+            PROF_ADD(0, 1, 0);  // search + set-up (incl. barrier)
+            PROF_ADD(kk, 2, 1); // pivot: 1 fast small, 2 fast singleton col, 3 general paths
+            sm->prof[3 + kk] += 1;                         // counts at 4,5,6
+            if (kk == 1) {
+                PROF_ADD(7, 3, 1);   // fast small: line updates (rest = finalize)
+                // the finalize step, relative to the barrier after the line updates (stamp 3)
+                PROF_ADD(22, 6, 3);   // wave 0: U row written
+                PROF_ADD(23, 24, 3);  // wave 1: L column written
+                PROF_ADD(24, 25, 3);  // wave 2: list update entered
+                PROF_ADD(25, 26, 25); //   links + tails loaded
+                PROF_ADD(26, 27, 26); //   runs resolved (LDS pointer jumping)
+                PROF_ADD(27, 28, 27); //   stores issued
+                PROF_ADD(30, 30, 27); //     of which: runs unlinked
+                PROF_ADD(31, 31, 30); //     tails resolved, same-key groups found
+                PROF_ADD(28, 29, 28); //   stores drained
+                PROF_ADD(29, 2, 29);  // list wave done -> all waves past the last barrier
+                // the line updates, seen by wave 1 (its first three tasks; the first is a column)
+                sm->prof[32] += sm->nzr - 1;                 // tasks: columns
+                sm->prof[33] += sm->nzc - 1;                 //        rows
+                PROF_ADD(34, 33, 1);  // loads of the first three tasks issued
+                PROF_ADD(35, 34, 33); // ... arrived
+                PROF_ADD(36, 35, 34); // first task done
+                PROF_ADD(37, 36, 35); // second task done
+                PROF_ADD(38, 37, 36); // third task done
+                PROF_ADD(39, 38, 37); // all of wave 1's tasks done, stores drained
+                PROF_ADD(40, 3, 38);  // ... until every wave is past the barrier
+                if (g_pstamp[44] > g_pstamp[1]) { // speculative search of the next pivot on the unlink wave, relative to stamp 1
+                    PROF_ADD(41, 41, 1);  // columns of the pivot row unlinked
+                    PROF_ADD(42, 42, 41); // walk
+                    PROF_ADD(43, 43, 42); // staging
+                    PROF_ADD(44, 44, 43); // reduction, result published
+                    sm->prof[45] += 1;
+                }
+            }
+            if (kk == 2) {
+                PROF_ADD2(0, 1, 0);   // search + set-up (incl. barrier) before a singleton-column pivot
+                // its finalize step, relative to the barrier after the column updates (stamp 48)
+                PROF_ADD2(1, 49, 48); // wave 0: early search (+ early set-up of the next pivot) done
+                PROF_ADD2(2, 50, 48); // U-row wave done
+                PROF_ADD2(3, 51, 48); // list wave: stores issued
+                PROF_ADD2(4, 2, 48);  // every wave past the barrier
+                PROF_ADD2(5, 48, 1);  // column updates (incl. barrier)
+            }
+            if (kk != 3) { // stages of the flattened search (stamps 8..14 set inside markowitz_fast)
+                PROF_ADD(8, 8, 0);   // head barrier -> search entered
+                PROF_ADD(9, 9, 8);   // walk: list heads + K link/meta loads
+                PROF_ADD(10, 10, 9); // candidate entries + row metadata, costs
+                PROF_ADD(11, 11, 10); // argmin
+                PROF_ADD(12, 12, 11); // pivot column to LDS + pivot row load
+                PROF_ADD(13, 13, 12); // column metadata + column hash
+                PROF_ADD(14, 14, 13); // row hash + room sums
+                PROF_ADD(15, 1, 14); // barrier after the search
+                // inside "candidate entries + row metadata": loads drained separately (PROF_WAIT)
+                if (g_pstamp[16] > g_pstamp[8]) { // (not a column-singleton search: those take mk_express)
+                    PROF_ADD(16, 17, 16); // entries: address arithmetic + load + drain
+                    PROF_ADD(17, 18, 17); // row metadata: load + drain
+                    PROF_ADD(18, 10, 18); // LDS stores + costs
+                    // inside the walk
+                    PROF_ADD(19, 19, 8);  // list heads loaded
+                    PROF_ADD(20, 20, 19); // first candidate's link + metadata loaded
+                    sm->prof[21] += 1;
+                }
+            }
+        }
+    };
+#endif
     long long ew_mcb = 0; // wave 0: per-lane result of the early search, kept for its next search
     int ew_fb = 0;
     for (;;) {
@@ -1310,7 +1408,7 @@ __device__ __forceinline__ void pivot_loop_body(DevLU *Ds, int stop_at, Sm *sm, 
         const int4 dB = *reinterpret_cast<const int4 *>(&sm->nzc);     // nzc, nzr, pcb, prb
         const int4 dC = *reinterpret_cast<const int4 *>(&sm->fa.kind); // kind, where, anycancel, ncand
         if (dA.w) break;
-        const int pr = dA.x, pc = dA.y;
+        int pr = dA.x, pc = dA.y;
         if (pc < 0) { // no pivot found: the reference asserts (factorize_bump.rs:22)
             if (tid == 0) {
                 DEV_CHECK(S, false);
@@ -1335,12 +1433,55 @@ __device__ __forceinline__ void pivot_loop_body(DevLU *Ds, int stop_at, Sm *sm, 
         // ---- pivot(): the room check of pivot.rs:70-81 was made by the searching wave; dispatch (:84-94)
         if (dA.z) break;
         PROF_STAMP(1);
-        const int nz_col = dB.x, nz_row = dB.y;
+        const int nz_col = dB.x;
+        int nz_row = dB.y;
         const int kind = dC.x;
         bool ok = true;
         if (kind == 1) fast_small(D, sm, mc, pr, pc, nz_col, nz_row, ew_mcb, ew_fb);
-        else if (kind == 2) fast_scol(D, sm, mc, pr, pc, nz_row, dC.y, ew_mcb, ew_fb);
-        else {
+        else if (kind == 2) {
+            // A run of singleton-column pivots: while wave 0 could lay out the next one during the finalize step
+            // (scol_setup_next: sm->mg), the barrier that ends fast_scol is also the barrier after that set-up, and every
+            // wave goes straight on, on the other working set.  What thread 0 does between two pivots of the ordinary
+            // loop -- record the pivot, advance the rank, the search's bookkeeping of mk_pick -- is done here by one lane
+            // of a wave that has no column to update in a short row; nothing reads these words before the next barrier.
+            Fast *cs = &sm->fa;
+            int wq = dC.y;
+            for (;;) {
+                fast_scol(D, sm, mc, cs, pr, pc, nz_row, wq, ew_mcb, ew_fb);
+                if (!sm->mg) break;
+#ifdef BLU_PROFILE
+                PROF_STAMP(2);
+                if (tid == 0) {
+                    prof_account(2);
+                    sm->prof2[6] += 1; // pivots entered through the merged barrier
+                    g_pstamp[0] = g_pstamp[1] = g_pstamp[2]; // (no loop head, no search: the next pivot starts here)
+                }
+#endif
+                const int4 nx = *reinterpret_cast<const int4 *>(&sm->nx_pr); // pr, pc, nzr, where
+                if (tid == (int)blockDim.x - 128) { // lane 0 of the last wave but one (the last one unlinks)
+                    const int rank = sm->rank;
+                    D.pinv[pr] = rank;
+                    D.qinv[pc] = rank;
+                    D.prow[rank] = pr;
+                    D.pcol[rank] = pc;
+                    sm->rank = rank + 1;
+                    sm->nsearch += sm->nx_nsr;
+                    sm->min_colnz = 1;
+                    sm->nrun[0]++;
+                    sm->nrun[1]++;
+                }
+                pr = nx.x;
+                pc = nx.y;
+                nz_row = nx.z;
+                wq = nx.w;
+                cs = cs == &sm->fa ? &sm->fb : &sm->fa;
+#ifdef BLU_EWCHECK
+                __syncthreads(); // (the pivot is recorded)
+                if (w == 0) scol_setup_check(D, sm, mc, cs);
+                __syncthreads();
+#endif
+            }
+        } else {
             if (tid == 0) mc->dirty = 1; // the general paths work on global memory only
             if (nz_row == 1) ok = pivot_singleton_row(D, sm);
             else if (nz_col == 1) ok = pivot_singleton_col(D, sm);
@@ -1350,70 +1491,7 @@ __device__ __forceinline__ void pivot_loop_body(DevLU *Ds, int stop_at, Sm *sm, 
         if (!ok) break; // exit_code set, pivot stays pending
         PROF_STAMP(2);
 #ifdef BLU_PROFILE
-        // a stamp of a code path that did not run in this pivot is stale (or was never written): only differences of
-        // stamps taken in order inside THIS pivot are added
-#define PROF_ADD(k, a, b)                                                                                           \
-    do {                                                                                                            \
-        const long long d_ = g_pstamp[a] - g_pstamp[b];                                                             \
-        if (g_pstamp[b] >= g_pstamp[0] && d_ >= 0 && d_ < (1LL << 28)) sm->prof[k] += d_;                            \
-    } while (0)
-        if (tid == 0) {
-            const int kk = sm->fa.kind == 1 ? 1 : (sm->fa.kind == 2 ? 2 : 3);
-            PROF_ADD(0, 1, 0);  // search + set-up (incl. barrier)
-            PROF_ADD(kk, 2, 1); // pivot: 1 fast small, 2 fast singleton col, 3 general paths
-            sm->prof[3 + kk] += 1;                         // counts at 4,5,6
-            if (kk == 1) {
-                PROF_ADD(7, 3, 1);   // fast small: line updates (rest = finalize)
-                // the finalize step, relative to the barrier after the line updates (stamp 3)
-                PROF_ADD(22, 6, 3);   // wave 0: U row written
-                PROF_ADD(23, 24, 3);  // wave 1: L column written
-                PROF_ADD(24, 25, 3);  // wave 2: list update entered
-                PROF_ADD(25, 26, 25); //   links + tails loaded
-                PROF_ADD(26, 27, 26); //   runs resolved (LDS pointer jumping)
-                PROF_ADD(27, 28, 27); //   stores issued
-                PROF_ADD(30, 30, 27); //     of which: runs unlinked
-                PROF_ADD(31, 31, 30); //     tails resolved, same-key groups found
-                PROF_ADD(28, 29, 28); //   stores drained
-                PROF_ADD(29, 2, 29);  // list wave done -> all waves past the last barrier
-                // the line updates, seen by wave 1 (its first three tasks; the first is a column)
-                sm->prof[32] += sm->nzr - 1;                 // tasks: columns
-                sm->prof[33] += sm->nzc - 1;                 //        rows
-                PROF_ADD(34, 33, 1);  // loads of the first three tasks issued
-                PROF_ADD(35, 34, 33); // ... arrived
-                PROF_ADD(36, 35, 34); // first task done
-                PROF_ADD(37, 36, 35); // second task done
-                PROF_ADD(38, 37, 36); // third task done
-                PROF_ADD(39, 38, 37); // all of wave 1's tasks done, stores drained
-                PROF_ADD(40, 3, 38);  // ... until every wave is past the barrier
-                if (g_pstamp[44] > g_pstamp[1]) { // speculative search of the next pivot on the unlink wave, relative to stamp 1
-                    PROF_ADD(41, 41, 1);  // columns of the pivot row unlinked
-                    PROF_ADD(42, 42, 41); // walk
-                    PROF_ADD(43, 43, 42); // staging
-                    PROF_ADD(44, 44, 43); // reduction, result published
-                    sm->prof[45] += 1;
-                }
-            }
-            if (kk != 3) { // stages of the flattened search (stamps 8..14 set inside markowitz_fast)
-                PROF_ADD(8, 8, 0);   // head barrier -> search entered
-                PROF_ADD(9, 9, 8);   // walk: list heads + K link/meta loads
-                PROF_ADD(10, 10, 9); // candidate entries + row metadata, costs
-                PROF_ADD(11, 11, 10); // argmin
-                PROF_ADD(12, 12, 11); // pivot column to LDS + pivot row load
-                PROF_ADD(13, 13, 12); // column metadata + column hash
-                PROF_ADD(14, 14, 13); // row hash + room sums
-                PROF_ADD(15, 1, 14); // barrier after the search
-                // inside "candidate entries + row metadata": loads drained separately (PROF_WAIT)
-                if (g_pstamp[16] > g_pstamp[8]) { // (not a column-singleton search: those take mk_express)
-                    PROF_ADD(16, 17, 16); // entries: address arithmetic + load + drain
-                    PROF_ADD(17, 18, 17); // row metadata: load + drain
-                    PROF_ADD(18, 10, 18); // LDS stores + costs
-                    // inside the walk
-                    PROF_ADD(19, 19, 8);  // list heads loaded
-                    PROF_ADD(20, 20, 19); // first candidate's link + metadata loaded
-                    sm->prof[21] += 1;
-                }
-            }
-        }
+        if (tid == 0) prof_account(kind);
 #endif
 
         // ---- remove columns whose maximum dropped below abstol (pivot.rs:98-106), record the pivot
@@ -1457,8 +1535,10 @@ __device__ __forceinline__ void pivot_loop_body(DevLU *Ds, int stop_at, Sm *sm, 
         S->nexpand += sm->nexpand;
         S->d3_hits += sm->d3;
         for (int k = 0; k < 6; k++) S->npivot_kind[k] += sm->kinds[k];
+        for (int k = 0; k < 2; k++) S->nrun[k] += sm->nrun[k];
 #ifdef BLU_PROFILE
         for (int k = 0; k < 48; k++) S->prof[k] += sm->prof[k];
+        for (int k = 0; k < 8; k++) S->prof2[k] += sm->prof2[k];
 #endif
         if (sm->exit_code == ST_ERROR && g_pivot_err_line) set_error(S, ST_ERROR, g_pivot_err_line);
         if (S->status == ST_RUNNING) S->status = sm->exit_code;

@@ -963,7 +963,10 @@ __device__ __forceinline__ bool markowitz_fast(const DevGP &D, Sm *sm, Mc *mc, l
         const int fb = ew_fb;
         nsr = fa->ewNsr;
         wave_mem_sync();
-        if (lane == 0) fa->ewValid = 0;
+        if (lane == 0) {
+            if (!whole) sm->nrun[0]++;
+            fa->ewValid = 0;
+        }
 #ifdef BLU_EWCHECK
         { // self-checking build: the ordinary search must give the same candidates, costs and count
             const int sN = fa->ncand;
@@ -1428,10 +1431,9 @@ __device__ __forceinline__ int wave_min_key(const int *keys, int n, int big)
 }
 
 // U row from the LDS copies (pivot.rs:306-312): slots q0..q1 of the pivot row except skipq
-__device__ __forceinline__ void fast_write_u(const DevGP &D, Sm *sm, int q0, int q1, int skipq)
+__device__ __forceinline__ void fast_write_u(const DevGP &D, Sm *sm, const Fast *fa, int q0, int q1, int skipq)
 {
     const int lane = lane_id();
-    Fast *fa = &sm->fa;
     int put = sm->uused;
     for (int c = q0; c <= q1; c += 64) {
         const int q = c + lane;
@@ -1494,7 +1496,8 @@ __device__ __forceinline__ void fast_write_l(const DevGP &D, Sm *sm)
 // cancellation fix-up is pending, row search is on, the long form of the list update was taken.
 // ------------------------------------------------------------------------------------------------
 // ebase = slot of elems[0] in the pivot row (the e1 arrays are indexed by slot)
-__device__ __forceinline__ void early_search(const DevGP &D, Sm *sm, Mc *mc, const int *elems, const int *keys, const int *begs, const double *maxs,
+// cs = working set of the pivot being finished (membership of its row's columns); the result is staged in sm->fa
+__device__ __forceinline__ void early_search(const DevGP &D, Sm *sm, Mc *mc, const Fast *cs, const int *elems, const int *keys, const int *begs, const double *maxs,
                                              int n, int ebase, long long &ew_mcb, int &ew_fb)
 {
     const int lane = lane_id();
@@ -1517,7 +1520,7 @@ __device__ __forceinline__ void early_search(const DevGP &D, Sm *sm, Mc *mc, con
         const unsigned long long one = __ballot(kq == 1);
         int j = -1, cb = 0, fs = -1;
         double cmx = 0.0;
-        if (h1 < m && !hcol_has(fa, h1)) {
+        if (h1 < m && !hcol_has(cs, h1)) {
             j = h1;
             cb = D.cbeg[j];
             cmx = D.colmax[j];
@@ -1910,10 +1913,10 @@ __device__ __forceinline__ void fast_small(const DevGP &D, Sm *sm, Mc *mc, int p
     // [2] count lists, [3] U row and the pivot's own bookkeeping; with fewer than 4 waves (or row search)
     // wave 0 writes the U row instead and the next search waits for the barrier
     const bool spec = early && (w == 0 || w == nw - 1) && spec_cond(sm, fa->tNew + 1, rnz1);
-    if (w == 0 && early && !spec) early_search(D, sm, mc, fa->tJ + 1, fa->tNew + 1, fa->tB + 1, fa->tMx + 1, rnz1, 1, ew_mcb, ew_fb);
+    if (w == 0 && early && !spec) early_search(D, sm, mc, fa, fa->tJ + 1, fa->tNew + 1, fa->tB + 1, fa->tMx + 1, rnz1, 1, ew_mcb, ew_fb);
     if (w == nw - 1 && spec) spec_finish(D, sm, rnz1);
     if (w == (early ? 3 : 0)) {
-        fast_write_u(D, sm, 1, rnz1, -1);
+        fast_write_u(D, sm, fa, 1, rnz1, -1);
         if (lane == 0) {
             D.colmax[pc] = fa->pcV[0];
             D.clen[pc] = 0;
@@ -1948,6 +1951,139 @@ __device__ __forceinline__ void fast_small(const DevGP &D, Sm *sm, Mc *mc, int p
 }
 
 // ------------------------------------------------------------------------------------------------
+// Early set-up inside a run of singleton-column pivots.  LP-like bases have their singleton-column pivots in ONE run (C3:
+// 49 999 in a row from the first pivot of the bump), so inside it every pivot is fast_scol followed by fast_scol.  When
+// early_search has staged the next column singleton, wave 0 goes on -- still beside the list append and the U row of the
+// pivot being finished -- with what the kind-2 part of mk_pick would do after the barrier: pivot row, metadata of its
+// columns, column hash, dispatch words.  It writes the OTHER working set (sm->fa / sm->fb alternate), because the list
+// wave and the U-row wave are still reading the current one.  The barrier that ends the finalize step is then also the
+// barrier after the set-up: every wave goes straight into the next fast_scol -- two barriers per pivot instead of three,
+// and no loop head, pick-up and set-up alone on wave 0 while fifteen waves wait.
+//   * Everything is read from global memory, which the barrier before the finalize step has made final for all that a
+//     singleton-column pivot changes in lines other than its own (length, maximum and entries of the row's columns;
+//     rows do not change) -- except the count-list links, which the list wave is rewriting at this moment: they are NOT
+//     staged (tLnk = 0, the unlink wave loads them after the barrier: the form that exists for long rows).
+//   * uused advances in this same finalize step, on the U-row wave, by at most rl_cur - 1: the room check uses that
+//     bound (whichever of the two values of sm->uused it reads); when it fails the ordinary set-up makes the exact check.
+//   * Anything unusual leaves the run: the staged search stays (ewValid) and the next pivot goes through the ordinary
+//     loop head, pick-up and mk_pick, which also raise the errors and the NEED_* exits.
+// Returns true when *nxt and the sm->nx_* words describe the next pivot.  `make ewcheck` compares each such set-up with
+// mk_express + mk_pick (scol_setup_check).
+// ------------------------------------------------------------------------------------------------
+__device__ __forceinline__ bool scol_setup_next(const DevGP &D, Sm *sm, Mc *mc, Fast *nxt, int rl_cur)
+{
+    const int lane = lane_id();
+    Fast *st = &sm->fa; // where early_search stages
+    if (st->ewValid != 1) return false;
+    if (g_pivot_err || mc->dirty) return false;
+    const int nrd = sm->rank + 1 + sm->rankdef; // what the loop head would see
+    if (nrd >= D.m || (sm->stop_at >= 0 && nrd >= sm->stop_at)) return false;
+    const int pc = st->cJ[0], pr = st->sI[0], prb = st->sB[0], nzr = st->sL[0];
+    if (nzr < 2 || nzr >= 64) return false;
+    if (sm->lused > D.lcap || (long long)sm->uused + (rl_cur - 1) + (nzr - 1) > (long long)D.ucap) return false;
+    const int jq0 = lane < nzr ? D.ridx[prb + lane] : -1;
+    for (int s = lane; s < HCOL; s += 64) nxt->hCol[s] = ~0ull;
+    const unsigned long long hb = __ballot(jq0 == pc);
+    if (!hb) return false; // (the ordinary set-up raises the error)
+    const int wpos = __ffsll((long long)hb) - 1;
+    if (lane < nzr) {
+        const int tb = D.cbeg[jq0], tl = D.clen[jq0], tc = D.ccap[jq0];
+        nxt->tJ[lane] = jq0;
+        nxt->tB[lane] = tb;
+        nxt->tL[lane] = tl;
+        nxt->tC[lane] = tc;
+        hcol_insert(nxt, jq0, lane);
+    }
+    if (lane == 0) {
+        nxt->pcI[0] = pr;
+        nxt->pcV[0] = st->sV[0];
+        nxt->prB[0] = prb;
+        nxt->prL[0] = nzr;
+        nxt->prC[0] = st->sC[0];
+        nxt->kind = 2;
+        nxt->where = wpos;
+        nxt->tLnk = 0;
+        sm->nx_pr = pr;
+        sm->nx_pc = pc;
+        sm->nx_nzr = nzr;
+        sm->nx_where = wpos;
+        sm->nx_prb = prb;
+        sm->nx_pcb = st->cB[0];
+        sm->nx_nsr = st->ewNsr;
+        st->ewValid = 0;
+    }
+    return true;
+}
+
+#ifdef BLU_EWCHECK
+// Self-checking build: the set-up that scol_setup_next made (*nxt, sm->nx_*) against mk_express + mk_pick.  Wave 0 runs it
+// between two extra barriers, once the pivot before is recorded and its list update complete -- the state the ordinary
+// set-up would have found.  mk_pick lays its result out in sm->fa: when that is the set under test, its slots are moved
+// to sm->fb first (the set of the finished pivot, free by now), and the pivot goes on with mk_pick's own lay-out.
+__device__ __forceinline__ void scol_setup_check(const DevGP &D, Sm *sm, Mc *mc, Fast *nxt)
+{
+    const int lane = lane_id();
+    Fast *T = nxt;
+    Fast *R = &sm->fa;
+    if (nxt == R) {
+        T = &sm->fb;
+        T->tJ[lane] = R->tJ[lane];
+        T->tB[lane] = R->tB[lane];
+        T->tL[lane] = R->tL[lane];
+        T->tC[lane] = R->tC[lane];
+        for (int s = lane; s < HCOL; s += 64) T->hCol[s] = R->hCol[s];
+        if (lane == 0) {
+            T->kind = R->kind;
+            T->where = R->where;
+            T->pcI[0] = R->pcI[0];
+            T->pcV[0] = R->pcV[0];
+        }
+    }
+    wave_mem_sync();
+    const int o_pr = sm->pr, o_pc = sm->pc, o_pcb = sm->pcb, o_prb = sm->prb, o_nzc = sm->nzc, o_nzr = sm->nzr;
+    const int o_exit = sm->exit_code, o_need = sm->need, o_minc = sm->min_colnz;
+    const long long o_ns = sm->nsearch;
+    wave_mem_sync();
+    int nsr2 = 0;
+    bool okc = mk_express(D, sm, mc, nsr2);
+    if (okc) {
+        mk_pick(D, sm, 0, 0, nsr2, true);
+        wave_mem_sync();
+        const int n = sm->nx_nzr;
+        okc = sm->pr == sm->nx_pr && sm->pc == sm->nx_pc && sm->nzr == n && sm->nzc == 1 && sm->prb == sm->nx_prb && sm->pcb == sm->nx_pcb &&
+              nsr2 == sm->nx_nsr && sm->exit_code == o_exit && sm->min_colnz == o_minc && R->kind == 2 && T->kind == 2 && R->where == T->where &&
+              R->pcI[0] == T->pcI[0] && R->pcV[0] == T->pcV[0];
+        if (okc && lane < n) {
+            const int j = T->tJ[lane];
+            okc = R->tJ[lane] == j && R->tB[lane] == T->tB[lane] && R->tL[lane] == T->tL[lane] && R->tC[lane] == T->tC[lane] &&
+                  hcol_slot(R, j) == lane && hcol_slot(T, j) == lane;
+        }
+        int cntR = 0, cntT = 0; // nothing else in either hash
+        for (int s = lane; s < HCOL; s += 64) {
+            cntR += __popcll(__ballot(R->hCol[s] != ~0ull));
+            cntT += __popcll(__ballot(T->hCol[s] != ~0ull));
+        }
+        okc = okc && cntR == n && cntT == n;
+    }
+    wave_mem_sync();
+    if (lane == 0) { // what mk_pick booked for a pivot that is already under way
+        sm->pr = o_pr;
+        sm->pc = o_pc;
+        sm->pcb = o_pcb;
+        sm->prb = o_prb;
+        sm->nzc = o_nzc;
+        sm->nzr = o_nzr;
+        sm->exit_code = o_exit;
+        sm->need = o_need;
+        sm->min_colnz = o_minc;
+        sm->nsearch = o_ns;
+    }
+    if (__ballot(!okc)) DEV_CHECK(D.s, false);
+    wave_mem_sync();
+}
+#endif
+
+// ------------------------------------------------------------------------------------------------
 // kind 2: pivot_singleton_col (pivot.rs:928-1025), whole workgroup
 // (Round 2 also built this pivot kind -- half of all pivots, in long runs -- as a single-wave route with search
 // and elimination fused, no workgroup barrier, the pivot row in the registers of wave 0 and a register stash
@@ -1956,12 +2092,13 @@ __device__ __forceinline__ void fast_small(const DevGP &D, Sm *sm, Mc *mc, int p
 // dependent look-ups of the search 3 300, stores and bookkeeping 1 800 -- cost the 6.8 us that the sixteen-wave
 // route with its three barriers costs: 820 -> 885 ms at C3.  Not kept.)
 // ------------------------------------------------------------------------------------------------
-__device__ __forceinline__ void fast_scol(const DevGP &D, Sm *sm, Mc *mc, int pr, int pc, int rl, int wq, long long &ew_mcb, int &ew_fb)
+// fa = the working set of this pivot: sm->fa as mk_pick laid it out, or the set that scol_setup_next laid out during
+// the finalize step of the previous pivot (sm->fa and sm->fb alternate inside a run of singleton-column pivots)
+__device__ __forceinline__ void fast_scol(const DevGP &D, Sm *sm, Mc *mc, Fast *fa, int pr, int pc, int rl, int wq, long long &ew_mcb, int &ew_fb)
 {
     const int w = wave_id(), nw = num_waves(), lane = lane_id();
     const int m = D.m;
     Scalars *S = D.s;
-    Fast *fa = &sm->fa;
     DEV_CHECK(S, fa->pcV[0] != 0.0 && fa->pcI[0] == pr);
 
     // (as in fast_small: with 8 or more waves the last one unlinks the row's columns from their count lists
@@ -2068,9 +2205,18 @@ __device__ __forceinline__ void fast_scol(const DevGP &D, Sm *sm, Mc *mc, int pr
     __syncthreads();
     // finalize step: [0] the search of the next pivot, [1] count lists, [2] U row and bookkeeping
     const bool early = split && !D.search_rows;
-    if (w == 0 && early) early_search(D, sm, mc, fa->tJ, fa->tNew, fa->tB, fa->tMx, rl, 0, ew_mcb, ew_fb);
+    PROF_STAMP(48);
+    if (w == 0) {
+        bool merged = false;
+        if (early) {
+            early_search(D, sm, mc, fa, fa->tJ, fa->tNew, fa->tB, fa->tMx, rl, 0, ew_mcb, ew_fb);
+            merged = scol_setup_next(D, sm, mc, fa == &sm->fa ? &sm->fb : &sm->fa, rl);
+        }
+        if (lane == 0) sm->mg = merged ? 1 : 0; // read by every wave right after the barrier below
+        PROF_STAMP(49);
+    }
     if (w == (early ? 2 : 0)) {
-        fast_write_u(D, sm, 0, rl - 1, wq);
+        fast_write_u(D, sm, fa, 0, rl - 1, wq);
         if (lane == 0) {
             D.lbeg[sm->rank + 1] = sm->lused; // empty column in L
             D.colmax[pc] = fa->pcV[0];
@@ -2078,17 +2224,21 @@ __device__ __forceinline__ void fast_scol(const DevGP &D, Sm *sm, Mc *mc, int pr
             D.rlen[pr] = 0;
             sm->kinds[1]++;
         }
+        if (w != 0) PROF_STAMP_L0(50);
     }
     if (w == 1 % nw) {
         if (D.search_rows && lane == 0) list_remove1(D.rflink, D.rblink, pr);
         // the pivot column sits at slot `where` of the row with key -1: it is unlinked as `gone`
-        const int mn = split ? wave_list_append_set(LC, m, fa->tJ, fa->tNew, rl, m + 2, fa->kg[0], mc->pFl)
-                             : wave_list_move_batch_set(LC, m, fa->tJ, fa->tNew, rl, InHCol{fa, 0, wq}, m + 2, pc, fa->kg[0]);
+        const int mn = split ? wave_list_append_set(LC, m, fa->tJ, fa->tNew, rl, m + 2, sm->fa.kg[0], mc->pFl)
+                             : wave_list_move_batch_set(LC, m, fa->tJ, fa->tNew, rl, InHCol{fa, 0, wq}, m + 2, pc, sm->fa.kg[0]);
         if (lane == 0 && mn < sm->min_colnz) sm->min_colnz = mn;
         if (lane == 0) { // what the next search may reuse (a column that sank below abstol cancels it: dirty)
-            mc->prevValid = split ? 1 : 0;
+            // (the ordinary search reads the previous pivot from sm->fa only: a run that ends on the other set leaves
+            // nothing to reuse, and that search -- one per run -- reads memory, which is always current)
+            mc->prevValid = split && fa == &sm->fa ? 1 : 0;
             mc->prevBase = 0;
         }
+        if (w != 0) PROF_STAMP_L0(51);
     }
     __syncthreads();
 }

@@ -40,3 +40,13 @@ print("fast small, line updates as wave 1 sees them: %.1f column + %.1f row task
 ne = max(1, p[45])
 print("speculative search on the unlink wave, beside the line updates (%d of %d ran to the end): unlink done @%.0f | walk %.0f | staging %.0f | reduction %.0f cycles"
       % (p[45], n1, p[41] / ne, p[42] / ne, p[43] / ne, p[44] / ne))
+# singleton-column pivots (keys 131..137: Scalars::prof2) and the run counters (121, 122)
+q = [h.stat(131 + k) for k in range(8)]
+n2 = max(1, p[5])
+us = lambda x: x * f / n2
+print("scol pivots : search+setup %.2f us each (%.0f%% of kernel) + pivot %.2f us each (%.0f%%) = %.0f%% of kernel time"
+      % (us(q[0]), 100 * q[0] / tot, us(p[2]), 100 * p[2] / tot, 100 * (q[0] + p[2]) / tot))
+print("scol pivot  : column updates incl. barrier %.2f us | finalize step, after its barrier: wave 0 (early search%s) done @%.2f us, U-row wave @%.2f us, list wave @%.2f us, all waves past the barrier @%.2f us"
+      % (us(q[5]), " + early set-up" if q[6] else "", us(q[1]), us(q[2]), us(q[3]), us(q[4])))
+print("scol run    : %d singleton-column pivots, search found early for %d (stat 121), set-up done early and barrier merged for %d (stat 122); %d entered through the merged barrier"
+      % (p[5], h.stat(121), h.stat(122), q[6]))
