@@ -90,12 +90,13 @@ struct Scalars {
     long long d3_hits;    // cancellations at pivot-column position >= 32 (reference defect D3 would diverge)
     long long npivot_kind[6];  // counters: 0 singleton row, 1 singleton col, 2 doubleton, 3 small, 4 any, 5 empty col
     long long nfast[4];        // k_pivot_loop_wave: pivots taken by its flattened paths (small, singleton col), searches handed over by the previous pivot
-    long long nrun[2];         // k_pivot_loop: singleton-column pivots whose search was found early / whose set-up was done early too (barrier merged)
+    long long nrun[4];         // k_pivot_loop: singleton-column pivots whose search was found early / whose set-up was done early too (barrier merged);
+                               // small pivots entered through a merged barrier / singleton-column pivots entered so after a small pivot
     double min_pivot, max_pivot;
     double onenorm, infnorm;
     double norm_l, norm_u, normest_l_inv, normest_u_inv, condest_l, condest_u, residual_test;
     long long prof[48];    // diagnostic build only (-DBLU_PROFILE): shader-clock ticks per phase of the pivot loop
-    long long prof2[8];    // the same, k_pivot_loop only: singleton-column pivots (search + set-up, finalize step per wave)
+    long long prof2[14];   // the same, k_pivot_loop only: singleton-column pivots (search + set-up, finalize step per wave); small pivots by how they were entered
 };
 
 // Scalar members of the descriptor: dimensions, parameters (public fields of struct LU,

@@ -562,7 +562,10 @@ extern "C" double blu_hip_get_stat(const blu_hip *h, int key)
     case 118: return (double)h->last_pivot_kernel; // which pivot kernel the last factorize of this handle ran: 0 k_pivot_loop, 1 k_pivot_loop_wave, 3 k_pivot_loop_wave2 (2 is not used)
     case 119: return (double)s.fill_paths; // bit 0 / bit 1: k_prep / k_finish filled through buckets (k_bucket.h)
     case 121: case 122: return (double)s.nrun[key - 121]; // k_pivot_loop, singleton-column pivots: search found early / set-up done early as well (two barriers instead of three)
-    case 131: case 132: case 133: case 134: case 135: case 136: case 137: case 138: return (double)s.prof2[key - 131]; // diagnostic build only
+    case 123: return (double)s.nrun[2]; // k_pivot_loop, barrier merged as for 122: small pivots set up during the finalize step of their predecessor
+    case 125: return (double)s.nrun[3]; // ... singleton-column pivots set up during the finalize step of a small pivot (124 is BLU_STAT_UPDATE_COST)
+    case 131: case 132: case 133: case 134: case 135: case 136: case 137: case 138: case 139: case 140: case 141: case 142: case 143: case 144:
+        return (double)s.prof2[key - 131]; // diagnostic build only
     case 57: return (double)s.err_line;
     case 58: return (double)s.status;
     case 60: case 61: case 62: case 63: case 64: case 65: case 66: case 67: case 68: case 69: case 70: case 71: case 72: case 73: case 74: case 75:

@@ -84,20 +84,24 @@ struct alignas(16) Sm {
     };
 #ifdef BLU_PROFILE
     long long prof[48];
-    long long prof2[8];
+    long long prof2[14];
 #else
     long long prof[1];
 #endif
 #if !BLU_CFG_WAVE
-    // runs of singleton-column pivots (scol_setup_next, k_pivot_fast.hip): the second working set, and the dispatch words
+    // merged barriers (scol_setup_next, small_setup_next, k_pivot_fast.hip): the second working set, and the dispatch words
     // of a pivot that was set up during the finalize step of its predecessor
     Fast fb;
     struct alignas(16) {
         int nx_pr, nx_pc, nx_nzr, nx_where;
     };
-    int nx_prb, nx_pcb, nx_nsr;
+    struct alignas(16) {
+        int nx_nzc, nx_kind, nx_pcb, nx_prb;
+    };
+    int nx_nsr, nx_minc; // what the search books: columns searched, count of its first candidate (min_colnz)
+    int nx_whole;        // 1: set up after a whole speculative search (small_setup_next), 0: after a column singleton found early
     int mg; // 1: the barrier that ended the finalize step was also the barrier after the next pivot's set-up
-    long long nrun[2];
+    long long nrun[4];
 #endif
     int rank, rankdef, min_colnz, min_rownz;
     int cused, rused, lused, uused;
@@ -1262,10 +1266,10 @@ __device__ __forceinline__ void pivot_loop_body(DevLU *Ds, int stop_at, Sm *sm, 
         sm->fa.spOk = 0;
         for (int k = 0; k < 6; k++) sm->kinds[k] = 0;
         sm->mg = 0;
-        sm->nrun[0] = sm->nrun[1] = 0;
+        sm->nrun[0] = sm->nrun[1] = sm->nrun[2] = sm->nrun[3] = 0;
 #ifdef BLU_PROFILE
         for (int k = 0; k < 48; k++) sm->prof[k] = 0;
-        for (int k = 0; k < 8; k++) sm->prof2[k] = 0;
+        for (int k = 0; k < 14; k++) sm->prof2[k] = 0;
         for (int k = 0; k < 56; k++) g_pstamp[k] = 0;
 #endif
     }
@@ -1296,13 +1300,19 @@ __device__ __forceinline__ void pivot_loop_body(DevLU *Ds, int stop_at, Sm *sm, 
         const long long d_ = g_pstamp[a] - g_pstamp[b];                                                             \
         if (g_pstamp[b] >= g_pstamp[0] && d_ >= 0 && d_ < (1LL << 28)) sm->prof2[k] += d_;                           \
     } while (0)
-    auto prof_account = [&](int kind_done) { // thread 0, after a pivot
+    auto prof_account = [&](int kind_done, int nzc_done, int nzr_done) { // thread 0, after a pivot
         {
             const int kk = kind_done == 1 ? 1 : (kind_done == 2 ? 2 : 3);
             PROF_ADD(0, 1, 0);  // search + set-up (incl. barrier)
             PROF_ADD(kk, 2, 1); // pivot: 1 fast small, 2 fast singleton col, 3 general paths
             sm->prof[3 + kk] += 1;                         // counts at 4,5,6
             if (kk == 1) {
+                // whole time of a small pivot from the barrier (or the loop head) it started at to the barrier that ends it,
+                // split by how it was entered: through a merged barrier (stamps 0 and 1 are then that barrier's) or the head
+                const int by = g_pstamp[1] == g_pstamp[0] ? 8 : 11;
+                PROF_ADD2(by, 2, 0);     // barrier to barrier, search + set-up included where it had one
+                PROF_ADD2(by + 1, 2, 3); // of which: the finalize step (with the early set-up of the next pivot, if made)
+                sm->prof2[by + 2] += 1;
                 PROF_ADD(7, 3, 1);   // fast small: line updates (rest = finalize)
                 // the finalize step, relative to the barrier after the line updates (stamp 3)
                 PROF_ADD(22, 6, 3);   // wave 0: U row written
@@ -1316,8 +1326,8 @@ __device__ __forceinline__ void pivot_loop_body(DevLU *Ds, int stop_at, Sm *sm, 
                 PROF_ADD(28, 29, 28); //   stores drained
                 PROF_ADD(29, 2, 29);  // list wave done -> all waves past the last barrier
                 // the line updates, seen by wave 1 (its first three tasks; the first is a column)
-                sm->prof[32] += sm->nzr - 1;                 // tasks: columns
-                sm->prof[33] += sm->nzc - 1;                 //        rows
+                sm->prof[32] += nzr_done - 1;                // tasks: columns
+                sm->prof[33] += nzc_done - 1;                //        rows
                 PROF_ADD(34, 33, 1);  // loads of the first three tasks issued
                 PROF_ADD(35, 34, 33); // ... arrived
                 PROF_ADD(36, 35, 34); // first task done
@@ -1331,6 +1341,11 @@ __device__ __forceinline__ void pivot_loop_body(DevLU *Ds, int stop_at, Sm *sm, 
                     PROF_ADD(43, 43, 42); // staging
                     PROF_ADD(44, 44, 43); // reduction, result published
                     sm->prof[45] += 1;
+                }
+                if (g_pstamp[46] > g_pstamp[3]) { // early set-up of the next pivot on the same wave, relative to the barrier after the line updates
+                    PROF_ADD(46, 45, 3);  // spec_finish done
+                    PROF_ADD(47, 46, 3);  // set-up done (or given up)
+                    sm->prof2[7] += 1;
                 }
             }
             if (kk == 2) {
@@ -1433,51 +1448,65 @@ __device__ __forceinline__ void pivot_loop_body(DevLU *Ds, int stop_at, Sm *sm, 
         // ---- pivot(): the room check of pivot.rs:70-81 was made by the searching wave; dispatch (:84-94)
         if (dA.z) break;
         PROF_STAMP(1);
-        const int nz_col = dB.x;
+        int nz_col = dB.x;
         int nz_row = dB.y;
-        const int kind = dC.x;
+        int kind = dC.x;
         bool ok = true;
-        if (kind == 1) fast_small(D, sm, mc, pr, pc, nz_col, nz_row, ew_mcb, ew_fb);
-        else if (kind == 2) {
-            // A run of singleton-column pivots: while wave 0 could lay out the next one during the finalize step
-            // (scol_setup_next: sm->mg), the barrier that ends fast_scol is also the barrier after that set-up, and every
-            // wave goes straight on, on the other working set.  What thread 0 does between two pivots of the ordinary
-            // loop -- record the pivot, advance the rank, the search's bookkeeping of mk_pick -- is done here by one lane
-            // of a wave that has no column to update in a short row; nothing reads these words before the next barrier.
+        if (kind == 1 || kind == 2) {
+            // While the next pivot could be laid out during the finalize step of this one (small_setup_next, scol_setup_next:
+            // sm->mg), the barrier that ends fast_small / fast_scol is also the barrier after that set-up, and every wave goes
+            // straight on, on the other working set: two barriers per pivot instead of three, and no loop head, pick-up and
+            // set-up alone on wave 0.  What thread 0 does between two pivots of the ordinary loop -- record the pivot, advance
+            // the rank, the search's bookkeeping of mk_pick -- is done here by one lane of a wave that takes no line update
+            // first.  Before a singleton-column pivot that is the last wave but one, and nothing reads these words before
+            // the next barrier (fast_scol reads rank, lused and uused in its finalize step only).  Before a small pivot it is
+            // the last wave itself, because its speculative walk reads the rank and min_colnz beside the line updates: the
+            // wave that reads them has written them, and no other wave reads them before the barrier after the line updates
+            // (fast_write_u / fast_write_l, the set-ups and early_search all run in the finalize step).
             Fast *cs = &sm->fa;
             int wq = dC.y;
             for (;;) {
-                fast_scol(D, sm, mc, cs, pr, pc, nz_row, wq, ew_mcb, ew_fb);
+                if (kind == 1) fast_small(D, sm, mc, cs, pr, pc, nz_col, nz_row, ew_mcb, ew_fb);
+                else fast_scol(D, sm, mc, cs, pr, pc, nz_row, wq, ew_mcb, ew_fb);
                 if (!sm->mg) break;
+                const int4 nx = *reinterpret_cast<const int4 *>(&sm->nx_pr);  // pr, pc, nzr, where
+                const int4 ny = *reinterpret_cast<const int4 *>(&sm->nx_nzc); // nzc, kind, pcb, prb
 #ifdef BLU_PROFILE
                 PROF_STAMP(2);
                 if (tid == 0) {
-                    prof_account(2);
-                    sm->prof2[6] += 1; // pivots entered through the merged barrier
+                    prof_account(kind, nz_col, nz_row);
+                    if (ny.y == 2) sm->prof2[6] += 1; // singleton-column pivots entered through the merged barrier
                     g_pstamp[0] = g_pstamp[1] = g_pstamp[2]; // (no loop head, no search: the next pivot starts here)
                 }
 #endif
-                const int4 nx = *reinterpret_cast<const int4 *>(&sm->nx_pr); // pr, pc, nzr, where
-                if (tid == (int)blockDim.x - 128) { // lane 0 of the last wave but one (the last one unlinks)
+                if (tid == (int)blockDim.x - (ny.y == 1 ? 64 : 128)) {
                     const int rank = sm->rank;
                     D.pinv[pr] = rank;
                     D.qinv[pc] = rank;
                     D.prow[rank] = pr;
                     D.pcol[rank] = pc;
                     sm->rank = rank + 1;
+                    sm->flops += (long long)(nz_col - 1) * (long long)(nz_row - 1);
                     sm->nsearch += sm->nx_nsr;
-                    sm->min_colnz = 1;
-                    sm->nrun[0]++;
-                    sm->nrun[1]++;
+                    sm->min_colnz = sm->nx_minc;
+                    if (!sm->nx_whole) sm->nrun[0]++; // (markowitz_fast counts a column singleton found early)
+                    if (kind == 2 && ny.y == 2) sm->nrun[1]++;
+                    if (ny.y == 1) sm->nrun[2]++;
+                    if (kind == 1 && ny.y == 2) sm->nrun[3]++;
                 }
                 pr = nx.x;
                 pc = nx.y;
                 nz_row = nx.z;
                 wq = nx.w;
+                nz_col = ny.x;
+                kind = ny.y;
                 cs = cs == &sm->fa ? &sm->fb : &sm->fa;
 #ifdef BLU_EWCHECK
                 __syncthreads(); // (the pivot is recorded)
-                if (w == 0) scol_setup_check(D, sm, mc, cs);
+                if (w == 0) {
+                    if (sm->nx_whole) small_setup_check(D, sm, mc, cs);
+                    else scol_setup_check(D, sm, mc, cs);
+                }
                 __syncthreads();
 #endif
             }
@@ -1491,7 +1520,7 @@ __device__ __forceinline__ void pivot_loop_body(DevLU *Ds, int stop_at, Sm *sm, 
         if (!ok) break; // exit_code set, pivot stays pending
         PROF_STAMP(2);
 #ifdef BLU_PROFILE
-        if (tid == 0) prof_account(kind);
+        if (tid == 0) prof_account(kind, nz_col, nz_row);
 #endif
 
         // ---- remove columns whose maximum dropped below abstol (pivot.rs:98-106), record the pivot
@@ -1535,10 +1564,10 @@ __device__ __forceinline__ void pivot_loop_body(DevLU *Ds, int stop_at, Sm *sm, 
         S->nexpand += sm->nexpand;
         S->d3_hits += sm->d3;
         for (int k = 0; k < 6; k++) S->npivot_kind[k] += sm->kinds[k];
-        for (int k = 0; k < 2; k++) S->nrun[k] += sm->nrun[k];
+        for (int k = 0; k < 4; k++) S->nrun[k] += sm->nrun[k];
 #ifdef BLU_PROFILE
         for (int k = 0; k < 48; k++) S->prof[k] += sm->prof[k];
-        for (int k = 0; k < 8; k++) S->prof2[k] += sm->prof2[k];
+        for (int k = 0; k < 14; k++) S->prof2[k] += sm->prof2[k];
 #endif
         if (sm->exit_code == ST_ERROR && g_pivot_err_line) set_error(S, ST_ERROR, g_pivot_err_line);
         if (S->status == ST_RUNNING) S->status = sm->exit_code;

@@ -1049,12 +1049,11 @@ __device__ __forceinline__ bool markowitz_fast(const DevGP &D, Sm *sm, Mc *mc, l
 // ------------------------------------------------------------------------------------------------
 // idx_first/val_first: this lane's entry of the first 64-entry chunk, loaded by the caller ahead of
 // time (the caller issues the loads of all its tasks before processing any of them)
-__device__ __forceinline__ void fast_col(const DevGP &D, Sm *sm, Mc *mc, int q, double *work, int idx_first, double val_first, int pr, int cnz1,
-                                         double pivot)
+__device__ __forceinline__ void fast_col(const DevGP &D, Sm *sm, Mc *mc, Fast *fa, int q, double *work, int idx_first, double val_first, int pr,
+                                         int cnz1, double pivot)
 {
     const int lane = lane_id();
     Scalars *S = D.s;
-    Fast *fa = &sm->fa;
     const int j = fa->tJ[q], cb = fa->tB[q], cl = fa->tL[q], cap = fa->tC[q];
 
     int nkept = 0, where = -1, first_idx = 0;
@@ -1193,12 +1192,11 @@ __device__ __forceinline__ int hrow_lookup2(const Fast *f, int k)
     if (!(h0 || e0 || h1 || e1)) r = hrow_lookup(f, k); // a third probe: rare (tables at most a quarter full)
     return r;
 }
-__device__ __forceinline__ void fast_col_short(const DevGP &D, Sm *sm, Mc *mc, int q, double *work, int idx, double val, int pr, int cnz1,
-                                               double pivot)
+__device__ __forceinline__ void fast_col_short(const DevGP &D, Sm *sm, Mc *mc, Fast *fa, int q, double *work, int idx, double val, int pr,
+                                               int cnz1, double pivot)
 {
     const int lane = lane_id();
     Scalars *S = D.s;
-    Fast *fa = &sm->fa;
     const int j = fa->tJ[q], cb = fa->tB[q], cl = fa->tL[q], cap = fa->tC[q];
     const bool v = lane < cl;
     const int mk = v ? hrow_lookup2(fa, idx) : 0;
@@ -1283,11 +1281,10 @@ __device__ __forceinline__ void fast_col_short(const DevGP &D, Sm *sm, Mc *mc, i
 
 // kind 1: row p of the pivot column, ONE wave.  Appends the whole pivot-row pattern; positions
 // cancelled by fast_col are removed afterwards by fast_fixrow.
-__device__ __forceinline__ void fast_row(const DevGP &D, Sm *sm, int p, int j_first, int pc, int rnz1)
+__device__ __forceinline__ void fast_row(const DevGP &D, Sm *sm, Fast *fa, int p, int j_first, int pc, int rnz1)
 {
     const int lane = lane_id();
     Scalars *S = D.s;
-    Fast *fa = &sm->fa;
     const int i = fa->pcI[p], rb = fa->prB[p], rl = fa->prL[p], cap = fa->prC[p];
 
     int nk = 0;
@@ -1354,11 +1351,10 @@ __device__ __forceinline__ bool hcol_has2(const Fast *f, int k)
     if (!(h0 || e0 || h1 || e1)) r = hcol_has(f, k);
     return r;
 }
-__device__ __forceinline__ void fast_row_short(const DevGP &D, Sm *sm, int p, int j, int pc, int rnz1)
+__device__ __forceinline__ void fast_row_short(const DevGP &D, Sm *sm, Fast *fa, int p, int j, int pc, int rnz1)
 {
     const int lane = lane_id();
     Scalars *S = D.s;
-    Fast *fa = &sm->fa;
     const int i = fa->pcI[p], rb = fa->prB[p], rl = fa->prL[p], cap = fa->prC[p];
     const bool v = lane < rl;
     const bool keep = v && !hcol_has2(fa, j);
@@ -1399,11 +1395,9 @@ __device__ __forceinline__ void fast_row_short(const DevGP &D, Sm *sm, int p, in
 // single updates with loads that were not issued ahead, and the per-lane selects of the pair set-up cost what the
 // shared instruction stream saves.  Not kept.)
 // rewrite the appended part of row p without the cancelled positions (pivot.rs:752-758)
-__device__ __forceinline__ void fast_fixrow(const DevGP &D, Sm *sm, int p)
+__device__ __forceinline__ void fast_fixrow(const DevGP &D, Fast *fa, int p, int rnz1)
 {
     const int lane = lane_id();
-    Fast *fa = &sm->fa;
-    const int rnz1 = sm->nzr - 1;
     const int dst = fa->rDst[p], nk = fa->rKept[p];
     int na = 0;
     for (int c = 0; c < rnz1; c += 64) {
@@ -1455,11 +1449,9 @@ __device__ __forceinline__ void fast_write_u(const DevGP &D, Sm *sm, const Fast 
 }
 
 // L column from the LDS copy (pivot.rs:404-416): slots 1..cnz1
-__device__ __forceinline__ void fast_write_l(const DevGP &D, Sm *sm)
+__device__ __forceinline__ void fast_write_l(const DevGP &D, Sm *sm, const Fast *fa, int cnz1)
 {
     const int lane = lane_id();
-    Fast *fa = &sm->fa;
-    const int cnz1 = sm->nzc - 1;
     const double pivot = fa->pcV[0];
     int put = sm->lused;
     for (int c = 1; c <= cnz1; c += 64) {
@@ -1505,7 +1497,7 @@ __device__ __forceinline__ void early_search(const DevGP &D, Sm *sm, Mc *mc, con
     Fast *fa = &sm->fa;
     const int K = D.maxsearch;
     if (D.search_rows || D.no_fast || K < 1 || K > KCMAX || m >= (1 << 27) || n >= 64) return;
-    if (sm->flag_small || fa->anycancel) return;
+    if (sm->flag_small || cs->anycancel) return;
     const int left = m - (sm->rank + 1) - sm->rankdef; // active columns at the next search
     if (left < 1) return;
     // my moved column (lane q < n): its new count
@@ -1677,11 +1669,11 @@ __device__ __forceinline__ void spec_walk(const DevGP &D, Sm *sm, Mc *mc)
 // After the barrier that ends the line updates: can the walk above still become the next search?  Evaluated by the
 // wave that walked (it goes on to stage the entries, spec_finish) and by wave 0 (it looks for a column singleton
 // instead if not, early_search): the same LDS words, the same answer.  keys = new counts of the n moved columns.
-__device__ __forceinline__ bool spec_cond(const Sm *sm, const int *keys, int n)
+// cs = working set of the pivot being finished (the walk's own words are staging fields: sm->fa always)
+__device__ __forceinline__ bool spec_cond(const Sm *sm, const Fast *cs, const int *keys, int n)
 {
     const int lane = lane_id();
-    const Fast *fa = &sm->fa;
-    if (!fa->spOk || sm->flag_small || fa->anycancel || n >= 64) return false;
+    if (!sm->fa.spOk || sm->flag_small || cs->anycancel || n >= 64) return false;
     const int kq = lane < n ? keys[lane] : 0x7fffffff;
     return __ballot(kq <= 0) == 0ull; // (an empty column: the ordinary search takes it, markowitz.rs:73-78)
 }
@@ -1691,7 +1683,8 @@ __device__ __forceinline__ bool spec_cond(const Sm *sm, const int *keys, int n)
 // the line updates -- the cost of every eligible entry, the winner.  Publishes the result for the next search
 // (ewValid = 2).  (Staging before the barrier and only the costs here was measured too: the barrier comes later
 // by more than this step gets shorter, 699 -> 707 ms.)
-__device__ __forceinline__ void spec_finish(const DevGP &D, Sm *sm, int n)
+// cs = working set of the pivot being finished: new counts, begins and maxima of the columns it updated
+__device__ __forceinline__ void spec_finish(const DevGP &D, Sm *sm, const Fast *cs, int n)
 {
     const int lane = lane_id();
     Fast *fa = &sm->fa;
@@ -1705,7 +1698,7 @@ __device__ __forceinline__ void spec_finish(const DevGP &D, Sm *sm, int n)
     // and the first K positions are the candidates of the next search.
     {
         const int lastnz = fa->spLastNz;
-        const int key = lane < n ? fa->tNew[1 + lane] : 0x7fffffff;
+        const int key = lane < n ? cs->tNew[1 + lane] : 0x7fffffff;
         const unsigned long long inb = __ballot(key < lastnz);
         if (inb) {
             int uJ = 0, uNz = 0x7fffffff, uB = 0, uL = 0;
@@ -1738,11 +1731,11 @@ __device__ __forceinline__ void spec_finish(const DevGP &D, Sm *sm, int n)
                 fa->cMx[posU] = uMx;
             }
             if (((inb >> lane) & 1ull) && posM < ncand) {
-                fa->cJ[posM] = fa->tJ[1 + lane];
+                fa->cJ[posM] = cs->tJ[1 + lane];
                 fa->cNz[posM] = key;
-                fa->cB[posM] = fa->tB[1 + lane];
+                fa->cB[posM] = cs->tB[1 + lane];
                 fa->cL[posM] = key;
-                fa->cMx[posM] = fa->tMx[1 + lane];
+                fa->cMx[posM] = cs->tMx[1 + lane];
             }
             wave_mem_sync();
             if (lane == 0) {
@@ -1806,11 +1799,15 @@ __device__ __forceinline__ void spec_finish(const DevGP &D, Sm *sm, int n)
 // ------------------------------------------------------------------------------------------------
 // kind 1, whole workgroup
 // ------------------------------------------------------------------------------------------------
-__device__ __forceinline__ void fast_small(const DevGP &D, Sm *sm, Mc *mc, int pr, int pc, int nzc, int nzr, long long &ew_mcb, int &ew_fb)
+__device__ __forceinline__ bool scol_setup_next(const DevGP &D, Sm *sm, Mc *mc, Fast *nxt, int rl_cur);
+__device__ __forceinline__ bool small_setup_next(const DevGP &D, Sm *sm, Mc *mc, Fast *nxt, int cnz1_cur, int rnz1_cur);
+// fa = the working set of this pivot: sm->fa as mk_pick laid it out, or the set that small_setup_next / scol_setup_next laid
+// out during the finalize step of the previous pivot (sm->fa and sm->fb alternate while barriers are merged).  The staging
+// fields (c*, s*, ew*, sp*, kg) are those of sm->fa always.
+__device__ __forceinline__ void fast_small(const DevGP &D, Sm *sm, Mc *mc, Fast *fa, int pr, int pc, int nzc, int nzr, long long &ew_mcb, int &ew_fb)
 {
     const int w = wave_id(), nw = num_waves(), lane = lane_id();
     const int m = D.m;
-    Fast *fa = &sm->fa;
     const int cnz1 = nzc - 1, rnz1 = nzr - 1;
     const double pivot = fa->pcV[0];
     DEV_CHECK(D.s, pivot != 0.0);
@@ -1885,11 +1882,11 @@ __device__ __forceinline__ void fast_small(const DevGP &D, Sm *sm, Mc *mc, int p
         for (int u = 0; u < 3; u++) {
             const int t = tt[u];
             if (t < rnz1) {
-                if (ll[u] <= 64) fast_col_short(D, sm, mc, t + 1, work, li[u], lv[u], pr, cnz1, pivot);
-                else fast_col(D, sm, mc, t + 1, work, li[u], lv[u], pr, cnz1, pivot);
+                if (ll[u] <= 64) fast_col_short(D, sm, mc, fa, t + 1, work, li[u], lv[u], pr, cnz1, pivot);
+                else fast_col(D, sm, mc, fa, t + 1, work, li[u], lv[u], pr, cnz1, pivot);
             } else if (t < ntask) {
-                if (ll[u] <= 64) fast_row_short(D, sm, t - rnz1 + 1, li[u], pc, rnz1);
-                else fast_row(D, sm, t - rnz1 + 1, li[u], pc, rnz1);
+                if (ll[u] <= 64) fast_row_short(D, sm, fa, t - rnz1 + 1, li[u], pc, rnz1);
+                else fast_row(D, sm, fa, t - rnz1 + 1, li[u], pc, rnz1);
             }
 #ifdef BLU_PROFILE
             if (w == 1 && base == 0) PROF_STAMP_L0(35 + u);
@@ -1906,15 +1903,33 @@ __device__ __forceinline__ void fast_small(const DevGP &D, Sm *sm, Mc *mc, int p
     __syncthreads();
     PROF_STAMP(3);
     if (fa->anycancel) {
-        for (int p = 1 + w; p <= cnz1; p += nw) fast_fixrow(D, sm, p);
+        for (int p = 1 + w; p <= cnz1; p += nw) fast_fixrow(D, fa, p, rnz1);
         __syncthreads();
     }
     // finalize step, one job per wave: [0] the search of the NEXT pivot (early_search), [1] L column,
     // [2] count lists, [3] U row and the pivot's own bookkeeping; with fewer than 4 waves (or row search)
-    // wave 0 writes the U row instead and the next search waits for the barrier
-    const bool spec = early && (w == 0 || w == nw - 1) && spec_cond(sm, fa->tNew + 1, rnz1);
-    if (w == 0 && early && !spec) early_search(D, sm, mc, fa, fa->tJ + 1, fa->tNew + 1, fa->tB + 1, fa->tMx + 1, rnz1, 1, ew_mcb, ew_fb);
-    if (w == nw - 1 && spec) spec_finish(D, sm, rnz1);
+    // wave 0 writes the U row instead and the next search waits for the barrier.
+    // The wave that found the next pivot goes on to set it up on the other working set (small_setup_next after a whole
+    // speculative search, scol_setup_next after a column singleton found by wave 0) and says so in sm->mg, which every
+    // wave reads right after the barrier below.  Exactly one wave writes that word: the speculating wave if the
+    // speculation holds (both waves evaluate spec_cond on the same LDS words), wave 0 otherwise.
+    const bool spec = early && (w == 0 || w == nw - 1) && spec_cond(sm, fa, fa->tNew + 1, rnz1);
+    Fast *other = fa == &sm->fa ? &sm->fb : &sm->fa;
+    if (w == 0 && !spec) {
+        bool merged = false;
+        if (early) {
+            early_search(D, sm, mc, fa, fa->tJ + 1, fa->tNew + 1, fa->tB + 1, fa->tMx + 1, rnz1, 1, ew_mcb, ew_fb);
+            merged = scol_setup_next(D, sm, mc, other, rnz1 + 1); // (the U row of this pivot: at most rnz1 entries)
+        }
+        if (lane == 0) sm->mg = merged ? 1 : 0;
+    }
+    if (w == nw - 1 && spec) {
+        spec_finish(D, sm, fa, rnz1);
+        PROF_STAMP_L0(45);
+        const bool merged = small_setup_next(D, sm, mc, other, cnz1, rnz1);
+        if (lane == 0) sm->mg = merged ? 1 : 0;
+        PROF_STAMP_L0(46);
+    }
     if (w == (early ? 3 : 0)) {
         fast_write_u(D, sm, fa, 1, rnz1, -1);
         if (lane == 0) {
@@ -1926,16 +1941,16 @@ __device__ __forceinline__ void fast_small(const DevGP &D, Sm *sm, Mc *mc, int p
         PROF_STAMP_L0(6);
     }
     if (w == 1 % nw) {
-        fast_write_l(D, sm);
+        fast_write_l(D, sm, fa, cnz1);
         PROF_STAMP_L0(24);
     }
     if (w == 2 % nw) {
         PROF_STAMP_L0(25);
-        const int mn = split ? wave_list_append_set(LC, m, fa->tJ + 1, fa->tNew + 1, rnz1, m + 2, fa->kg[0], mc->pFl + 1)
-                             : wave_list_move_batch_set(LC, m, fa->tJ + 1, fa->tNew + 1, rnz1, InHCol{fa, 1, 0}, m + 2, pc, fa->kg[0]);
+        const int mn = split ? wave_list_append_set(LC, m, fa->tJ + 1, fa->tNew + 1, rnz1, m + 2, sm->fa.kg[0], mc->pFl + 1)
+                             : wave_list_move_batch_set(LC, m, fa->tJ + 1, fa->tNew + 1, rnz1, InHCol{fa, 1, 0}, m + 2, pc, sm->fa.kg[0]);
         if (lane == 0 && mn < sm->min_colnz) sm->min_colnz = mn;
-        if (lane == 0) {
-            mc->prevValid = split ? 1 : 0;
+        if (lane == 0) { // (the ordinary search reads the previous pivot from sm->fa only, as in fast_scol)
+            mc->prevValid = split && fa == &sm->fa ? 1 : 0;
             mc->prevBase = 1;
         }
         PROF_WAIT();
@@ -1944,7 +1959,7 @@ __device__ __forceinline__ void fast_small(const DevGP &D, Sm *sm, Mc *mc, int p
     if (D.search_rows && w == 3 % nw) {
         if (lane == 0) list_remove1(D.rflink, D.rblink, pr); // pr is not in the row hash set: unlink it first
         wave_mem_sync();
-        const int mn = wave_list_move_batch_set(LinksG{D.rflink, D.rblink}, m, fa->pcI + 1, fa->rNew + 1, cnz1, InHRow{fa}, m + 2, -1, fa->kg[1]);
+        const int mn = wave_list_move_batch_set(LinksG{D.rflink, D.rblink}, m, fa->pcI + 1, fa->rNew + 1, cnz1, InHRow{fa}, m + 2, -1, sm->fa.kg[1]);
         if (lane == 0 && mn < sm->min_rownz) sm->min_rownz = mn;
     }
     __syncthreads();
@@ -2002,14 +2017,144 @@ __device__ __forceinline__ bool scol_setup_next(const DevGP &D, Sm *sm, Mc *mc, 
         nxt->prC[0] = st->sC[0];
         nxt->kind = 2;
         nxt->where = wpos;
+        nxt->anycancel = 0;
         nxt->tLnk = 0;
         sm->nx_pr = pr;
         sm->nx_pc = pc;
         sm->nx_nzr = nzr;
         sm->nx_where = wpos;
+        sm->nx_nzc = 1;
+        sm->nx_kind = 2;
         sm->nx_prb = prb;
         sm->nx_pcb = st->cB[0];
         sm->nx_nsr = st->ewNsr;
+        sm->nx_minc = 1;
+        sm->nx_whole = 0;
+        st->ewValid = 0;
+    }
+    return true;
+}
+
+// ------------------------------------------------------------------------------------------------
+// Early set-up after a whole speculative search.  When spec_finish has published the winner of the next search (ewValid
+// == 2, spKey), the same wave -- the last one, which has no other job in the finalize step -- goes on with what mk_pick
+// would do for that key after the barrier: pivot row and column from the staged candidates, pivot column -> LDS, pivot
+// row, metadata of its columns, both hashes, room sums, dispatch words.  It writes the OTHER working set, because the L,
+// U and list waves are still reading the current one, and the barrier that ends the finalize step is then also the
+// barrier after the set-up (sm->mg), as inside a run of singleton-column pivots.  Only the straight-line shape of mk_pick
+// is taken (row and column of at most 64 entries, kind 1 or 2).
+//   * Final at this moment, and read from global memory or from what spec_finish staged after the barrier: entries and
+//     (begin, len, cap) of every row and column, colmax, cused / rused.  The barrier after the line updates made them
+//     final; fast_fixrow runs only after a cancellation, and then nothing was speculated (spec_cond).  The finalize step
+//     itself stores to lines of the finished pivot only (its row and column get length 0): no active line refers to them.
+//   * Not final: the count-list links, which the list wave is rewriting.  They are not staged (tLnk = 0: the unlink wave
+//     loads them after the barrier, the form that exists for long rows).
+//   * Advancing in this same finalize step: lused by at most cnz1_cur on the L wave, uused by at most rnz1_cur on the U
+//     wave.  The room check uses those upper bounds, whichever of the two values it reads; when a bound fails the
+//     ordinary set-up makes the exact check and raises NEED_L / NEED_U.  When the arena estimate fails, the ordinary
+//     set-up hands the pivot to the general path, which makes the exact check -- as in mk_pick.
+//   * Anything unusual leaves through the ordinary head with the staged search intact (ewValid stays 2): an error flag,
+//     stale list heads, stop_at or the full rank reached, a shape outside the straight-line form.  A column below abstol,
+//     a cancellation, the row search and fewer than 8 waves never get here (spec_cond, `early`).  *nxt may have been
+//     written by then: nothing reads it (the ordinary search reuses the previous pivot from sm->fa only, and only when
+//     that pivot ran there).
+// Returns true when *nxt and the sm->nx_* words describe the next pivot.  `make ewcheck` compares each such set-up with
+// the ordinary search + mk_pick (small_setup_check).
+// ------------------------------------------------------------------------------------------------
+__device__ __forceinline__ bool small_setup_next(const DevGP &D, Sm *sm, Mc *mc, Fast *nxt, int cnz1_cur, int rnz1_cur)
+{
+    const int lane = lane_id();
+    Fast *st = &sm->fa; // where spec_finish stages
+    if (st->ewValid != 2) return false;
+    if (g_pivot_err || mc->dirty) return false;
+    const int nrd = sm->rank + 1 + sm->rankdef; // what the loop head would see
+    if (nrd >= D.m || (sm->stop_at >= 0 && nrd >= sm->stop_at)) return false;
+    const int ncand = st->ncand;
+    const int off1 = ncand > 1 ? st->cOff[1] : 0x7fffffff, off2 = ncand > 2 ? st->cOff[2] : 0x7fffffff,
+              off3 = ncand > 3 ? st->cOff[3] : 0x7fffffff;
+    const int fsel = (int)(st->spKey & 255LL);
+    const int csel = (fsel >= off1) + (fsel >= off2) + (fsel >= off3);
+    const int coff = st->cOff[csel];
+    const int pc = st->cJ[csel], pr = st->sI[fsel];
+    const int nzc = st->cL[csel], pcb = st->cB[csel], where = fsel - coff;
+    const int nzr = st->sL[fsel], prb = st->sB[fsel];
+    // (the shape test of mk_pick's straight-line form: a row of exactly 64 is in, for either kind -- fast_scol takes such a row
+    // from the ordinary head as well, with the unsplit form of its list update and nothing set up early behind it;
+    // scol_setup_next keeps to rows shorter than 64, the split form, which is all a run needs)
+    int kind = 0;
+    if (nzr >= 2 && nzr <= 64) {
+        if (nzc == 1) kind = 2;
+        else if (nzc >= 3 && nzc <= 64) kind = 1;
+    }
+    if (kind == 0) return false;
+    if ((long long)sm->lused + cnz1_cur + (nzc - 1) > (long long)D.lcap || (long long)sm->uused + rnz1_cur + (nzr - 1) > (long long)D.ucap) return false;
+    // ---- from here on as the straight-line form of mk_pick, on *nxt
+    const int jq0 = lane < nzr ? D.ridx[prb + lane] : -1;
+    if (kind == 1) {
+        for (int s = lane; s < HROW; s += 64) nxt->hRow[s] = ~0ull;
+    }
+    for (int s = lane; s < HCOL; s += 64) nxt->hCol[s] = ~0ull;
+    int hr_idx0 = 0, hr_slot0 = 0, hr_len0 = 0;
+    if (lane < nzc) {
+        const int slot = (lane == where) ? 0 : (lane == 0 ? where : lane);
+        const int idx = st->sI[coff + lane], rlv = st->sL[coff + lane];
+        nxt->pcI[slot] = idx;
+        nxt->pcV[slot] = st->sV[coff + lane];
+        nxt->prB[slot] = st->sB[coff + lane];
+        nxt->prL[slot] = rlv;
+        nxt->prC[slot] = st->sC[coff + lane];
+        hr_slot0 = slot;
+        hr_idx0 = idx;
+        hr_len0 = rlv;
+    }
+    const unsigned long long hb = __ballot(jq0 == pc);
+    if (!hb) return false; // (the ordinary set-up raises the error)
+    const int wpos = __ffsll((long long)hb) - 1;
+    int tb = 0, tl = 0, tc = 0;
+    if (lane < nzr) {
+        tb = D.cbeg[jq0];
+        tl = D.clen[jq0];
+        tc = D.ccap[jq0];
+    }
+    int gc = 0, gr = 0;
+    if (kind == 1 && hr_slot0 >= 1) {
+        hrow_insert(nxt, hr_idx0, hr_slot0);
+        const int n = hr_len0 + nzr - 1;
+        gr = n + stretch_of(D.stretch, n) + D.pad;
+    }
+    if (lane < nzr) {
+        const int slot = kind == 1 ? ((lane == wpos) ? 0 : (lane == 0 ? wpos : lane)) : lane;
+        nxt->tJ[slot] = jq0;
+        nxt->tB[slot] = tb;
+        nxt->tL[slot] = tl;
+        nxt->tC[slot] = tc;
+        hcol_insert(nxt, jq0, slot);
+        if (kind == 1 && lane != wpos) {
+            const int n = tl + nzc - 1;
+            gc = n + stretch_of(D.stretch, n) + D.pad;
+        }
+    }
+    if (kind == 1) {
+        const long long both = wave_sum_ll(((long long)gc << 32) | (long long)(unsigned)gr);
+        if ((long long)sm->cused + (both >> 32) > (long long)D.carena_cap || (long long)sm->rused + (both & 0xffffffffLL) > (long long)D.rarena_cap)
+            return false; // mk_pick hands such a pivot to the general path
+    }
+    if (lane == 0) {
+        nxt->kind = kind;
+        nxt->where = wpos;
+        nxt->anycancel = 0;
+        nxt->tLnk = 0;
+        sm->nx_pr = pr;
+        sm->nx_pc = pc;
+        sm->nx_nzr = nzr;
+        sm->nx_where = wpos;
+        sm->nx_nzc = nzc;
+        sm->nx_kind = kind;
+        sm->nx_prb = prb;
+        sm->nx_pcb = pcb;
+        sm->nx_nsr = st->ewNsr;
+        sm->nx_minc = st->cNz[0];
+        sm->nx_whole = 1;
         st->ewValid = 0;
     }
     return true;
@@ -2064,6 +2209,105 @@ __device__ __forceinline__ void scol_setup_check(const DevGP &D, Sm *sm, Mc *mc,
             cntT += __popcll(__ballot(T->hCol[s] != ~0ull));
         }
         okc = okc && cntR == n && cntT == n;
+    }
+    wave_mem_sync();
+    if (lane == 0) { // what mk_pick booked for a pivot that is already under way
+        sm->pr = o_pr;
+        sm->pc = o_pc;
+        sm->pcb = o_pcb;
+        sm->prb = o_prb;
+        sm->nzc = o_nzc;
+        sm->nzr = o_nzr;
+        sm->exit_code = o_exit;
+        sm->need = o_need;
+        sm->min_colnz = o_minc;
+        sm->nsearch = o_ns;
+    }
+    if (__ballot(!okc)) DEV_CHECK(D.s, false);
+    wave_mem_sync();
+}
+
+// The same for a set-up that small_setup_next made: the ordinary search of markowitz_fast (mk_express, else mk_walk +
+// mk_stage) and mk_pick, then every word of the working set that the pivot will read -- pivot column with the metadata of
+// its rows, pivot row with the metadata of its columns, both hashes including "nothing else in them", kind, where -- and
+// the sm words against sm->nx_*.
+__device__ __forceinline__ void small_setup_check(const DevGP &D, Sm *sm, Mc *mc, Fast *nxt)
+{
+    const int lane = lane_id();
+    Fast *T = nxt;
+    Fast *R = &sm->fa;
+    const int n = sm->nx_nzr, nc = sm->nx_nzc, knd = sm->nx_kind;
+    if (nxt == R) {
+        T = &sm->fb;
+        T->tJ[lane] = R->tJ[lane];
+        T->tB[lane] = R->tB[lane];
+        T->tL[lane] = R->tL[lane];
+        T->tC[lane] = R->tC[lane];
+        T->pcI[lane] = R->pcI[lane];
+        T->pcV[lane] = R->pcV[lane];
+        T->prB[lane] = R->prB[lane];
+        T->prL[lane] = R->prL[lane];
+        T->prC[lane] = R->prC[lane];
+        for (int s = lane; s < HCOL; s += 64) T->hCol[s] = R->hCol[s];
+        for (int s = lane; s < HROW; s += 64) T->hRow[s] = R->hRow[s];
+        if (lane == 0) {
+            T->kind = R->kind;
+            T->where = R->where;
+            T->anycancel = R->anycancel;
+        }
+    }
+    wave_mem_sync();
+    const int o_pr = sm->pr, o_pc = sm->pc, o_pcb = sm->pcb, o_prb = sm->prb, o_nzc = sm->nzc, o_nzr = sm->nzr;
+    const int o_exit = sm->exit_code, o_need = sm->need, o_minc = sm->min_colnz;
+    const long long o_ns = sm->nsearch;
+    wave_mem_sync();
+    // (the record step has set min_colnz to the early search's first count already: the walk here starts at count 1, so a
+    // column of a smaller count that the early search missed would be found)
+    if (lane == 0) sm->min_colnz = 1;
+    wave_mem_sync();
+    int nsr2 = 0;
+    bool okc = true;
+    if (mk_express(D, sm, mc, nsr2)) {
+        mk_pick(D, sm, 0, 0, nsr2, true);
+    } else if (mk_walk(D, sm, mc) == 0) {
+        long long mcb2;
+        int fb2;
+        mk_stage(D, sm, mcb2, fb2);
+        nsr2 = R->ncand;
+        mk_pick(D, sm, mcb2, fb2, nsr2, false);
+    } else {
+        okc = false;
+    }
+    wave_mem_sync();
+    if (okc) {
+        okc = sm->pr == sm->nx_pr && sm->pc == sm->nx_pc && sm->nzr == n && sm->nzc == nc && sm->prb == sm->nx_prb && sm->pcb == sm->nx_pcb &&
+              nsr2 == sm->nx_nsr && sm->exit_code == o_exit && sm->min_colnz == o_minc && sm->min_colnz == sm->nx_minc && R->kind == knd &&
+              T->kind == knd && R->where == T->where && R->where == sm->nx_where && R->anycancel == 0 && T->anycancel == 0;
+        if (okc && lane < n) {
+            const int j = T->tJ[lane];
+            okc = R->tJ[lane] == j && R->tB[lane] == T->tB[lane] && R->tL[lane] == T->tL[lane] && R->tC[lane] == T->tC[lane] &&
+                  hcol_slot(R, j) == lane && hcol_slot(T, j) == lane;
+        }
+        if (okc && lane < nc) {
+            const int i = T->pcI[lane];
+            okc = R->pcI[lane] == i && R->pcV[lane] == T->pcV[lane] && R->prB[lane] == T->prB[lane] && R->prL[lane] == T->prL[lane] &&
+                  R->prC[lane] == T->prC[lane];
+            if (okc && knd == 1 && lane >= 1) okc = hrow_lookup(R, i) == lane && hrow_lookup(T, i) == lane;
+        }
+        int cntR = 0, cntT = 0; // nothing else in either hash
+        for (int s = lane; s < HCOL; s += 64) {
+            cntR += __popcll(__ballot(R->hCol[s] != ~0ull));
+            cntT += __popcll(__ballot(T->hCol[s] != ~0ull));
+        }
+        okc = okc && cntR == n && cntT == n;
+        if (knd == 1) {
+            cntR = cntT = 0;
+            for (int s = lane; s < HROW; s += 64) {
+                cntR += __popcll(__ballot(R->hRow[s] != ~0ull));
+                cntT += __popcll(__ballot(T->hRow[s] != ~0ull));
+            }
+            okc = okc && cntR == nc - 1 && cntT == nc - 1;
+        }
     }
     wave_mem_sync();
     if (lane == 0) { // what mk_pick booked for a pivot that is already under way

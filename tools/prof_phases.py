@@ -41,7 +41,8 @@ ne = max(1, p[45])
 print("speculative search on the unlink wave, beside the line updates (%d of %d ran to the end): unlink done @%.0f | walk %.0f | staging %.0f | reduction %.0f cycles"
       % (p[45], n1, p[41] / ne, p[42] / ne, p[43] / ne, p[44] / ne))
 # singleton-column pivots (keys 131..137: Scalars::prof2) and the run counters (121, 122)
-q = [h.stat(131 + k) for k in range(8)]
+q = [h.stat(131 + k) for k in range(14)]
+q = [0 if x != x else x for x in q]  # (a library from before a statistic answers NaN)
 n2 = max(1, p[5])
 us = lambda x: x * f / n2
 print("scol pivots : search+setup %.2f us each (%.0f%% of kernel) + pivot %.2f us each (%.0f%%) = %.0f%% of kernel time"
@@ -50,3 +51,16 @@ print("scol pivot  : column updates incl. barrier %.2f us | finalize step, after
       % (us(q[5]), " + early set-up" if q[6] else "", us(q[1]), us(q[2]), us(q[3]), us(q[4])))
 print("scol run    : %d singleton-column pivots, search found early for %d (stat 121), set-up done early and barrier merged for %d (stat 122); %d entered through the merged barrier"
       % (p[5], h.stat(121), h.stat(122), q[6]))
+# small pivots entered through a merged barrier (statistics 123, 125): the finalize step of their predecessor, after its
+# barrier, on the speculating wave -- spec_finish done, then the early set-up done (or given up) -- against the helper waves
+ns = max(1, q[7])
+st = lambda k: 0 if h.stat(k) != h.stat(k) else h.stat(k)  # (a library from before these statistics answers NaN)
+print("small merge : %d of %d small pivots entered through the merged barrier (stat 123), %d singleton-column pivots after a small one (stat 125); speculating wave in %d finalize steps: spec_finish done @%.2f us, early set-up done @%.2f us (U row @%.2f, L column @%.2f us: the helpers wait from there)"
+      % (st(123), p[4], st(125), q[7], p[46] * f / ns, p[47] * f / ns, cyc(22) * f, cyc(23) * f))
+# the same pivots by how they were entered (keys 139..144): whole time from the barrier, or the loop head, a small pivot starts at
+# to the barrier that ends it -- search + set-up included where it had one of its own -- and its finalize step, which holds the
+# early set-up of the NEXT pivot where one was made
+for nm, k in (("merged barrier", 8), ("loop head", 11)):
+    n = max(1, q[k + 2])
+    print("small pivots entered through the %-14s: n=%d, %.2f us each barrier to barrier (%.0f%% of kernel), of which finalize step %.2f us"
+          % (nm, q[k + 2], q[k] * f / n, 100 * q[k] / tot, q[k + 1] * f / n))
