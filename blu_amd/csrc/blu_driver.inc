@@ -426,6 +426,8 @@ static bool batch_pivot_and_finish(BatchCtx &B)
                     if (chain_defect == 0) {
                         hipLaunchKernelGGL(k_stats_tail_a, dim3(TAIL_BLOCKS), dim3(1024), 0, B.stream, B.dD, B.dO, h0->gw);
                         hipLaunchKernelGGL(k_stats_tail_b, dim3(1), dim3(1024), 0, B.stream, B.dD, B.dO, h0->gw);
+                        // the work vectors of the chains and of the tail back to the all-zero state pivot_any expects
+                        (void)hipMemsetAsync(h0->D.gwork, 0, 7 * ((size_t)h0->m + 1) * sizeof(double), B.stream);
                     }
                 }
                 (void)hipEventRecord(t1, B.stream);

@@ -7,18 +7,27 @@
 // from global memory one and two steps ahead: a step then takes a global round trip (~0.85 us), because the
 // wave has to wait for the loads of this step before it can start the next.
 //
-// Here the wave that walks the chain never loads from global memory.  The other waves of the workgroup
+// Here the waves that walk the chain never load from global memory.  The other waves of the workgroup
 // (helpers) stream the operands of the coming steps into LDS rings -- step records (length, pivot, own value,
 // output index) and entries (value, and WHERE the operand of the work vector is found) -- hundreds of steps
-// ahead of the chain wave; the chain wave reads LDS only (the records of a block once, a step's fields by v_readlane;
-// the entries two steps ahead) and its step is the arithmetic: products, the ordered sum in the reference's order,
-// the step function (one f64 division), one LDS and one global store.  Work-vector operands come from
-//   * a window of the last CH_W results in LDS (xwin, written by the chain wave itself),
-//   * the previous step's result, forwarded in a register,
+// ahead of the chain; the chain reads LDS only (the records of a block once, a step's fields by v_readlane)
+// and its step is the arithmetic: products, the ordered sum in the reference's order, the step function (one
+// f64 division), one LDS and one global store.  Work-vector operands come from
+//   * a window of the last CH_W results in LDS (xwin, written by the chain),
 //   * for producers at least CH_FAR steps back: the value gathered from global memory by the helper (final by
-//     then: a helper stages a block only after the chain wave has published -- stores drained -- a progress
+//     then: a helper stages a block only after every ring wave has published -- stores drained -- a progress
 //     that puts every such producer behind it).  The leading terms of a step that are of this kind are added by
-//     the helper itself, in the step's order and with the chain wave's roundings: the chain wave starts behind them.
+//     the helper itself, in the step's order and with the chain's roundings: the chain starts behind them.
+//
+// The chain is walked by a RING of CH_R waves (waves 0..CH_R-1; ring wave r takes steps r, r + CH_R, ...), because
+// what step s truly waits for is little: of its ordered sum only the terms from the first one whose producer is
+// less than CH_R steps back, and the step function.  The record fields, the entries, the window operands of older
+// producers, their products and the leading part of the sum need nothing newer than step s - CH_R, which the wave
+// published itself, and every earlier step was published before that one: steps are published strictly in sweep
+// order (xwin slot, LDS fence, then tag[s & (CH_TG-1)] = s + 1; a step waits for its predecessor's tag before it
+// sets its own, also when it has no late term).  So a ring wave does that EARLY part while its predecessors are
+// still at work, waits for the tag of step s - 1, and the LATE part -- read the window for the late entries,
+// products, the rest of the sum in order, step function, publish -- is all that is left on the critical path.
 // Every sweep is in GATHER form: step k reads results of earlier steps only.  The reference's scatter-form
 // loops (x[i] -= t_k * a_ik over column k, k in sweep order) are run over the transposed storage -- row-wise L
 // ascending, U rows descending in the pivot order (k_rows_grid below) -- accumulating into the step's own
@@ -26,9 +35,11 @@
 //
 // Flow control (LDS, in-order per wave): helpers take blocks of CH_SB steps round-robin; the entry-ring base of a
 // block is handed from the helper of the previous block as soon as that one knows its entry count; a block is
-// staged only when its step-ring slots (chain CH_NB blocks behind) and its entry-ring space are free; the chain
-// wave waits for blk_ready of the block it enters.  Steps with more than 64 entries are not staged: the chain
-// wave takes them straight from global memory (its own stores are ordered before its later loads).
+// staged only when its step-ring slots (every ring wave CH_NB blocks behind) and its entry-ring space are free:
+// each ring wave drains its own stores when it leaves a block and publishes its own progress, and the room test
+// takes the minimum; a ring wave waits for blk_ready of the block it enters.  Steps with more than 64 entries are
+// not staged: the ring wave waits for its predecessor and takes the entries straight from global memory, each
+// operand from the window (producer less than CH_FAR back) or, final by the argument above, from global memory.
 #pragma once
 #include "blu_dev.h"
 
@@ -41,7 +52,10 @@
 #define CH_HAS 0x10000           // record: the step has entries (some or all may have gone into `init` already)
 #define CH_HT 16                 // hand-off ring of entry bases
 #define CH_SEL_FAR (-1)          // operand: the helper's gathered value
-#define CH_SEL_PREV (-2)         // operand: the previous step's result (register)
+#define CH_SEL_PREV (-2)         // operand: the previous step's result (its window slot)
+#define CH_R 4                   // ring waves (waves 0..CH_R-1); the workgroup's other waves are helpers
+#define CH_TG 64                 // ring of step tags
+#define CH_SPIN 64               // polls of a predecessor's tag before the wait starts to sleep between polls
 
 struct __attribute__((aligned(16))) ChRecA { // what the chain wave reads of a step, in two 16-byte LDS reads
     int n, eb, w, k;
@@ -63,8 +77,9 @@ struct ChainLds {
     volatile int blk_ready[CH_NB];
     volatile int eb_tag[CH_HT];
     volatile int eb_val[CH_HT];
-    volatile int chain_done; // blocks finished by the chain wave with their stores drained
-    volatile int chain_eb;   // entry-ring position of the first entry not consumed by those blocks
+    volatile int tag[CH_TG];        // tag[s & (CH_TG-1)] == s + 1: step s is in the window, and so is every earlier step
+    volatile int ring_done[CH_R];    // per ring wave: blocks it has finished with its stores drained
+    volatile int ring_eb[CH_R];      // per ring wave: entry-ring position of the first entry of the block it is in
     volatile int abort;      // a wait ran into its bound (a defect, never a valid state): everybody leaves
 };
 
@@ -80,19 +95,38 @@ struct ChEnt {
     double val;
 };
 
+// The flags other waves poll are volatile, and a volatile access through a generic pointer stays a FLAT instruction (the
+// address-space inference leaves volatile accesses alone): several times the latency of a ds_ instruction on every poll and
+// every publication.  They are read and written through these two, with the LDS address space spelled out.
+#ifdef BLU_EMU_BUILD
+#define CH_LDS(T) T *
+#else
+#define CH_LDS(T) __attribute__((address_space(3))) T *
+#endif
+__device__ __forceinline__ int ch_flag(const volatile int *p) { return *(CH_LDS(const volatile int))p; }
+__device__ __forceinline__ void ch_set(volatile int *p, int v) { *(CH_LDS(volatile int))p = v; }
+
 // Bounded wait on LDS state written by another wave: 2^24 polls of s_sleep(1) (of the order of a second) and the
 // sweep is abandoned with an error instead of hanging the GPU; the callers report the code to the host, which
-// never uses the results of an abandoned sweep.
-#define CH_WAIT(L, cond, code)                                         \
+// never uses the results of an abandoned sweep.  The first `spin` polls follow one another without a sleep (the
+// hand-over from step to step); `gave_up` is set when the wait ended without its condition.
+#define CH_WAIT_SPIN(L, cond, code, spin, gave_up)                  \
     do {                                                            \
         int it_ = 0;                                                \
         while (!(cond)) {                                           \
-            if ((L)->abort || ++it_ > (1 << 24)) {                  \
-                if (!(L)->abort) (L)->abort = (code);               \
+            if (++it_ <= (spin)) continue;                          \
+            if (ch_flag(&(L)->abort) || it_ > (1 << 24)) {                    \
+                if (!ch_flag(&(L)->abort)) ch_set(&(L)->abort, (code));               \
+                (gave_up) = true;                                   \
                 break;                                              \
             }                                                       \
             __builtin_amdgcn_s_sleep(1);                            \
         }                                                           \
+    } while (0)
+#define CH_WAIT(L, cond, code)                       \
+    do {                                             \
+        bool gu_ = false;                            \
+        CH_WAIT_SPIN(L, cond, code, 0, gu_);         \
     } while (0)
 
 #ifdef BLU_EMU_BUILD // (CPU emulation build: memory is always current; the DPP sum below through the emulator's exchange)
@@ -110,6 +144,19 @@ __device__ __forceinline__ double ch_load_final(gdouble_p p)
 }
 
 // ---- helper side: stage block b ---------------------------------------------------------------------------
+// room for block b, whose entries end at entry-ring position `top`: the slowest ring wave decides (each counter only
+// grows, so a value read a moment early errs on the safe side)
+__device__ __forceinline__ bool ch_room(ChainLds *L, int b, int top)
+{
+    int done = ch_flag(&L->ring_done[0]), eb = ch_flag(&L->ring_eb[0]);
+#pragma unroll
+    for (int r = 1; r < CH_R; r++) {
+        const int d = ch_flag(&L->ring_done[r]), e = ch_flag(&L->ring_eb[r]);
+        done = d < done ? d : done;
+        eb = e < eb ? e : eb;
+    }
+    return done >= b - CH_NB + 1 && top - eb <= CH_CE;
+}
 template <bool INIT_OWN, bool SUB, class A>
 __device__ __forceinline__ void ch_stage_block(const A &ad, ChainLds *L, int b, int k0, int dir, int nsteps, gdouble_p out)
 {
@@ -127,19 +174,19 @@ __device__ __forceinline__ void ch_stage_block(const A &ad, ChainLds *L, int b, 
     // entry-ring base: from the helper of the previous block
     int base = 0;
     if (b > 0) {
-        CH_WAIT(L, L->eb_tag[b & (CH_HT - 1)] == b, 1);
-        base = L->eb_val[b & (CH_HT - 1)];
+        CH_WAIT(L, ch_flag(&L->eb_tag[b & (CH_HT - 1)]) == b, 1);
+        base = ch_flag(&L->eb_val[b & (CH_HT - 1)]);
     }
     if (lane == 0) {
-        L->eb_val[(b + 1) & (CH_HT - 1)] = base + cnt;
+        ch_set(&L->eb_val[(b + 1) & (CH_HT - 1)], base + cnt);
         ch_lds_fence();
-        L->eb_tag[(b + 1) & (CH_HT - 1)] = b + 1;
+        ch_set(&L->eb_tag[(b + 1) & (CH_HT - 1)], b + 1);
     }
     // room: step-ring slots of block b - CH_NB, entry-ring space; this also makes every result further back
     // than the window final and visible (see the header)
-    CH_WAIT(L, L->chain_done >= b - CH_NB + 1 && base + cnt - L->chain_eb <= CH_CE, 2);
+    CH_WAIT(L, ch_room(L, b, base + cnt), 2);
     asm volatile("" ::: "memory");
-    if (L->abort) return;
+    if (ch_flag(&L->abort)) return;
     const int slot0 = s0 & (CH_CS - 1);
     if (mine) {
         const int sl = slot0 + lane;
@@ -231,7 +278,7 @@ __device__ __forceinline__ void ch_stage_block(const A &ad, ChainLds *L, int b, 
         }
     }
     ch_lds_fence();
-    if (lane == 0) L->blk_ready[b & (CH_NB - 1)] = b + 1;
+    if (lane == 0) ch_set(&L->blk_ready[b & (CH_NB - 1)], b + 1);
 }
 
 // ---- chain side -------------------------------------------------------------------------------------------
@@ -259,21 +306,6 @@ __device__ __forceinline__ ChRec ch_read_rec(ChainLds *L, int s)
     R.own = b.own;
     R.init = L->rinit[sl];
     return R;
-}
-__device__ __forceinline__ ChOps ch_read_ops(ChainLds *L, const ChRec &R)
-{
-    ChOps E;
-    E.val = 0.0;
-    E.xv = 0.0;
-    E.sel = CH_SEL_FAR;
-    if (lane_id() < (R.n & (CH_HAS - 1)) && R.n > 0) {
-        const int r = (R.eb + lane_id()) & (CH_CE - 1);
-        const ChOpsV v = L->ev[r];
-        E.val = v.val;
-        E.xv = v.xv;
-        E.sel = L->sel[r];
-    }
-    return E;
 }
 // acc -/+= the products of lanes 0..n-1, in lane order (the reference's sequential loop)
 template <bool SUB>
@@ -352,57 +384,54 @@ __device__ __forceinline__ double ch_accumulate_rows(double acc, double prod, in
     return acc;
 }
 
-// One sweep by the whole workgroup: wave 0 walks the chain, the other waves stage.  All waves must call it.
+// One sweep by the whole workgroup: waves 0..CH_R-1 walk the chain as a ring, the other waves stage.  All waves must call it.
 //   INIT_OWN: the accumulator starts at the step's own value (scatter-form loops of the reference), else at 0
 //   SUB:      terms are subtracted, else added
-//   f(k, has_entries, acc, own, diag) -> the step's result, stored to out[w] and the window; f may store more
+//   f(k, has_entries, acc, own, diag) -> the step's result, stored to out[w] and the window; f may store more, but it is
+//   called by whichever ring wave has the step: it must not carry state from step to step
 // The helpers add the leading terms whose producers are at least CH_FAR steps back (ch_stage_block).
 // On return every store of the sweep has completed and the workgroup is synchronised; false: abandoned (defect).
 template <bool INIT_OWN, bool SUB, class A, class F>
 __device__ __forceinline__ bool chain_sweep(const A &ad, ChainLds *L, int k0, int dir, int nsteps, gdouble_p out, F f)
 {
+    static_assert(CH_R >= 1 && CH_R <= CH_SB && CH_TG >= 2 * CH_R, "ring size");
     const int w = wave_id(), nw = num_waves(), lane = lane_id();
     const int nblk = (nsteps + CH_SB - 1) / CH_SB;
-    if (threadIdx.x < CH_NB) L->blk_ready[threadIdx.x] = 0;
-    if (threadIdx.x < CH_HT) L->eb_tag[threadIdx.x] = -1;
-    if (threadIdx.x == 0) {
-        L->chain_done = 0;
-        L->chain_eb = 0;
-        L->abort = 0;
+    if (threadIdx.x < CH_NB) ch_set(&L->blk_ready[threadIdx.x], 0);
+    if (threadIdx.x < CH_HT) ch_set(&L->eb_tag[threadIdx.x], -1);
+    if (threadIdx.x < CH_TG) ch_set(&L->tag[threadIdx.x], 0);
+    if (threadIdx.x < CH_R) {
+        ch_set(&L->ring_done[threadIdx.x], 0);
+        ch_set(&L->ring_eb[threadIdx.x], 0);
     }
+    if (threadIdx.x == 0) ch_set(&L->abort, 0);
     __syncthreads();
-    if (w > 0) {
-        for (int b = w - 1; b < nblk && !L->abort; b += nw - 1) ch_stage_block<INIT_OWN, SUB>(ad, L, b, k0, dir, nsteps, out);
-    } else if (nsteps > 0) {
+    if (w >= CH_R) {
+        for (int b = w - CH_R; b < nblk && !ch_flag(&L->abort); b += nw - CH_R) ch_stage_block<INIT_OWN, SUB>(ad, L, b, k0, dir, nsteps, out);
+    } else {
 #ifdef BLU_PROFILE
-        long long t_wait = 0, t_drain = 0;
+        long long t_wait = 0, t_tag = 0, t_drain = 0;
         const long long t_begin = (long long)__builtin_amdgcn_s_memtime();
 #endif
-        // The records of the steps past the end read as empty: the ring slots behind the last block are written
-        // as "n = 0" by nobody, so the look-ahead below is clamped to the last step instead.
-        const auto wait_block = [&](int b) {
-            if (b < nblk) {
-                CH_WAIT(L, L->blk_ready[b & (CH_NB - 1)] == b + 1, 3);
-                asm volatile("" ::: "memory");
-            }
-        };
         const int last = nsteps - 1;
-        // The records of a block are read once, 64 lanes at a time: lane t holds the record of step bs + t (lanes 32,
-        // 33 reach into the next block for the look-ahead) and a step takes its fields by v_readlane -- a handful of
-        // scalar moves instead of LDS reads, address arithmetic and a three-stage rotation of ten registers per step.
+        const int li = lane & 15;
+        __builtin_amdgcn_s_setprio(3); // (a ring wave shares its SIMD with helpers: the chain goes first)
+        // The records of a block are read once by every ring wave, lane t = step bs + t, and a step takes its fields by
+        // v_readlane -- a handful of scalar moves instead of LDS reads and address arithmetic per step.
         const auto rl_d = [](double x, int t) {
             const int lo = __builtin_amdgcn_readlane(__double2loint(x), t), hi = __builtin_amdgcn_readlane(__double2hiint(x), t);
             return __hiloint2double(hi, lo);
         };
-        const auto read_ops = [&](int eb, int nf) {
+        // n entries from entry-ring position eb: lane l has entry l; up to 16 entries: every row of 16 lanes has them all
+        // (ch_accumulate_rows).  A lane without an entry reads as a far operand with value 0.
+        const auto read_ops = [&](int eb, int n) {
             ChOps E;
             E.val = 0.0;
             E.xv = 0.0;
             E.sel = CH_SEL_FAR;
-            const int n = nf < 0 ? 0 : (nf & (CH_HAS - 1));
-            const int li = n <= 16 ? (lane & 15) : lane; // (up to 16 entries: every row of 16 lanes holds them all, ch_accumulate_rows)
-            if (li < n) {
-                const int r = (eb + li) & (CH_CE - 1);
+            const int l = n <= 16 ? li : lane;
+            if (l < n) {
+                const int r = (eb + l) & (CH_CE - 1);
                 const ChOpsV v = L->ev[r];
                 E.val = v.val;
                 E.xv = v.xv;
@@ -410,87 +439,168 @@ __device__ __forceinline__ bool chain_sweep(const A &ad, ChainLds *L, int k0, in
             }
             return E;
         };
-        wait_block(0);
+        int cur_b = -1;
         ChRec BR;
-        ChOps E1, E2;
-        double xw1 = 0.0, vprev = 0.0;
-        for (int b = 0; b < nblk && !L->abort; b++) {
-            // the look-ahead of this block's steps reaches two steps into the next block
+        BR.n = BR.eb = BR.w = BR.k = 0;
+        BR.diag = BR.own = BR.init = 0.0;
+        bool gave_up = false;
+        for (int s = w; s < nsteps && !gave_up; s += CH_R) {
+            const int b = s / CH_SB;
+            if (b != cur_b) {
+                // the wave leaves a block: its stores drained, then its progress
+                if (cur_b >= 0) {
 #ifdef BLU_PROFILE
-            const long long tw0 = (long long)__builtin_amdgcn_s_memtime();
+                    const long long td0 = (long long)__builtin_amdgcn_s_memtime();
 #endif
-            wait_block(b + 1);
+                    ch_vm_drain();
 #ifdef BLU_PROFILE
-            t_wait += (long long)__builtin_amdgcn_s_memtime() - tw0;
+                    t_drain += (long long)__builtin_amdgcn_s_memtime() - td0;
 #endif
-            const int bs = b * CH_SB;
-            {
-                const int sl = bs + lane;
+                    ch_lds_fence();
+                    if (lane == 0) ch_set(&L->ring_done[w], b);
+                }
+#ifdef BLU_PROFILE
+                const long long tw0 = (long long)__builtin_amdgcn_s_memtime();
+#endif
+                CH_WAIT_SPIN(L, ch_flag(&L->blk_ready[b & (CH_NB - 1)]) == b + 1, 3, 0, gave_up);
+                asm volatile("" ::: "memory");
+#ifdef BLU_PROFILE
+                t_wait += (long long)__builtin_amdgcn_s_memtime() - tw0;
+#endif
+                if (gave_up) break; // (the records are not there: nothing of this block may be used)
+                const int sl = b * CH_SB + lane;
                 BR = ch_read_rec(L, sl < last ? sl : last);
+                if (lane == 0) ch_set(&L->ring_eb[w], BR.eb);
+                cur_b = b;
             }
-            if (b == 0) {
-                E1 = read_ops(__builtin_amdgcn_readlane(BR.eb, 0), __builtin_amdgcn_readlane(BR.n, 0));
-                xw1 = E1.sel >= 0 ? L->xwin[E1.sel] : 0.0;
-                E2 = read_ops(__builtin_amdgcn_readlane(BR.eb, 1), __builtin_amdgcn_readlane(BR.n, 1));
-            }
-            const int ns = (bs + CH_SB < nsteps ? CH_SB : nsteps - bs);
-            for (int t = 0; t < ns; t++) {
-                // ahead: window operands of step s+1, entries of s+2
-                const double xw2 = E2.sel >= 0 ? L->xwin[E2.sel] : 0.0;
-                const ChOps E3 = read_ops(__builtin_amdgcn_readlane(BR.eb, t + 2), __builtin_amdgcn_readlane(BR.n, t + 2));
-                // step s = bs + t
-                const int nf = __builtin_amdgcn_readlane(BR.n, t), k1 = __builtin_amdgcn_readlane(BR.k, t), w1 = __builtin_amdgcn_readlane(BR.w, t);
-                const double own1 = rl_d(BR.own, t), diag1 = rl_d(BR.diag, t);
-                const int n1 = nf < 0 ? -1 : (nf & (CH_HAS - 1));
-                double acc = rl_d(BR.init, t);
-                if (n1 > 0) {
-                    const double x = E1.sel == CH_SEL_PREV ? vprev : (E1.sel >= 0 ? xw1 : E1.xv);
-                    if (n1 <= 16) acc = ch_accumulate_rows<SUB>(acc, (lane & 15) < n1 ? __dmul_rn(x, E1.val) : 0.0, n1);
-                    else acc = ch_accumulate<SUB>(acc, lane < n1 ? __dmul_rn(x, E1.val) : 0.0, n1);
-                } else if (n1 < 0) { // long step: straight from global memory
-                    const ChMeta M = ad.meta(k1);
-                    for (int o = 0; o < M.len; o += 64) {
-                        ChEnt E;
-                        E.pos = 0;
-                        E.gidx = 0;
-                        E.val = 0.0;
-                        const int nn = M.len - o < 64 ? M.len - o : 64;
-                        if (lane < nn) E = ad.ent(k1, M.b, o + lane);
-                        acc = ch_accumulate<SUB>(acc, lane < nn ? __dmul_rn(out[E.gidx], E.val) : 0.0, nn);
+            const int t = s - b * CH_SB;
+            const int nf = __builtin_amdgcn_readlane(BR.n, t), eb1 = __builtin_amdgcn_readlane(BR.eb, t);
+            const int k1 = __builtin_amdgcn_readlane(BR.k, t), w1 = __builtin_amdgcn_readlane(BR.w, t);
+            const double own1 = rl_d(BR.own, t), diag1 = rl_d(BR.diag, t);
+            const int n1 = nf < 0 ? -1 : (nf & (CH_HAS - 1));
+            double acc = rl_d(BR.init, t);
+            // the tag of step s - 1: every result up to it is in the window
+            const auto wait_prev = [&]() {
+                if (s > 0) {
+#ifdef BLU_PROFILE
+                    const long long tw0 = (long long)__builtin_amdgcn_s_memtime();
+#endif
+                    CH_WAIT_SPIN(L, ch_flag(&L->tag[(s - 1) & (CH_TG - 1)]) == s, 4, CH_SPIN, gave_up);
+#ifdef BLU_PROFILE
+                    t_tag += (long long)__builtin_amdgcn_s_memtime() - tw0;
+#endif
+                }
+                asm volatile("" ::: "memory");
+            };
+            // window slot of an operand and how many steps back its producer is (a far operand has neither)
+            const auto slot_of = [&](int sel) { return (sel == CH_SEL_PREV ? k1 - dir : sel) & (CH_W - 1); };
+            const auto dist_of = [&](int slot) { return ((k1 - slot) * dir) & (CH_W - 1); };
+            if (n1 > 0 && n1 <= 16) {
+                // EARLY: the leading terms up to the first one whose producer is less than CH_R steps back
+                const ChOps E = read_ops(eb1, n1);
+                const int slot = slot_of(E.sel);
+                const bool win = E.sel != CH_SEL_FAR;
+                const bool late = win && dist_of(slot) < CH_R;
+                const unsigned lm = (unsigned)__ballot(late) & 0xffffu;
+                const int p = lm ? __ffs((int)lm) - 1 : n1;
+                if (p > 0) {
+                    const double x = (win && !late) ? L->xwin[slot] : E.xv;
+                    acc = ch_accumulate_rows<SUB>(acc, li < p ? __dmul_rn(x, E.val) : 0.0, p);
+                }
+                if (p < n1) {
+                    // the terms from there on, moved down to lane 0: what is old enough is read and multiplied now ...
+                    const int nl = n1 - p;
+                    const ChOps EL = read_ops(eb1 + p, nl);
+                    const int slot_l = slot_of(EL.sel);
+                    const bool win_l = EL.sel != CH_SEL_FAR;
+                    const bool late_l = win_l && dist_of(slot_l) < CH_R;
+                    const double prod_e = __dmul_rn((win_l && !late_l) ? L->xwin[slot_l] : EL.xv, EL.val);
+                    wait_prev();
+                    // ... LATE: the window for the late entries, all lanes at once, and the rest of the sum in order
+                    const double prod_l = __dmul_rn(L->xwin[slot_l], EL.val);
+                    acc = ch_accumulate_rows<SUB>(acc, li < nl ? (late_l ? prod_l : prod_e) : 0.0, nl);
+                } else {
+                    wait_prev();
+                }
+            } else if (n1 > 16) { // rare: the whole sum after the wait
+                const ChOps E = read_ops(eb1, n1);
+                wait_prev();
+                const double x = E.sel != CH_SEL_FAR ? L->xwin[slot_of(E.sel)] : E.xv;
+                acc = ch_accumulate<SUB>(acc, lane < n1 ? __dmul_rn(x, E.val) : 0.0, n1);
+            } else if (n1 < 0) { // long step: straight from global memory; recent producers from the window
+                wait_prev();
+                const ChMeta M = ad.meta(k1);
+                for (int o = 0; o < M.len; o += 64) {
+                    ChEnt E;
+                    E.pos = k1 - dir * CH_FAR;
+                    E.gidx = 0;
+                    E.val = 0.0;
+                    const int nn = M.len - o < 64 ? M.len - o : 64;
+                    double x = 0.0;
+                    if (lane < nn) {
+                        E = ad.ent(k1, M.b, o + lane);
+                        const int d = (k1 - E.pos) * dir;
+                        x = (d > 0 && d < CH_FAR) ? L->xwin[E.pos & (CH_W - 1)] : ch_load_final(out + E.gidx);
                     }
+                    acc = ch_accumulate<SUB>(acc, lane < nn ? __dmul_rn(x, E.val) : 0.0, nn);
                 }
-                const double v = f(k1, nf != 0, acc, own1, diag1);
-                if (lane == 0) {
-                    L->xwin[k1 & (CH_W - 1)] = v;
-                    out[w1] = v;
-                }
-                vprev = v;
-                E1 = E2;
-                xw1 = xw2;
-                E2 = E3;
+            } else {
+                wait_prev();
             }
-            // block finished: drain the stores, publish (lane 32 of the records = the first step of the next block)
-#ifdef BLU_PROFILE
-            const long long td0 = (long long)__builtin_amdgcn_s_memtime();
-#endif
-            ch_vm_drain();
-#ifdef BLU_PROFILE
-            t_drain += (long long)__builtin_amdgcn_s_memtime() - td0;
-#endif
-            ch_lds_fence();
-            const int eb_next = __builtin_amdgcn_readlane(BR.eb, CH_SB);
-            if (lane == 0 && bs + CH_SB < nsteps) {
-                L->chain_eb = eb_next;
-                L->chain_done = b + 1;
+            if (gave_up) break; // (nothing is published: the others run into their own bounds or see L->abort)
+            const double v = f(k1, nf != 0, acc, own1, diag1);
+            if (lane == 0) {
+                L->xwin[k1 & (CH_W - 1)] = v;
+                ch_lds_fence();
+                ch_set(&L->tag[s & (CH_TG - 1)], s + 1);
+                out[w1] = v;
             }
         }
+        __builtin_amdgcn_s_setprio(0);
+        // the wave is through: its stores drained, and no helper waits for it any more
         ch_vm_drain();
+        ch_lds_fence();
+        if (lane == 0) {
+            ch_set(&L->ring_eb[w], 0x7fffffff);
+            ch_set(&L->ring_done[w], nblk + CH_NB);
+        }
 #ifdef BLU_PROFILE
-        if (lane == 0)
-            printf("chain sweep (block %d): %d steps, %.0f cycles/step, waiting for blocks %.0f, draining stores %.0f\n", (int)blockIdx.x, nsteps,
-                   (double)((long long)__builtin_amdgcn_s_memtime() - t_begin) / nsteps, (double)t_wait / nsteps, (double)t_drain / nsteps);
+        if (lane == 0 && nsteps > 0)
+            printf("chain sweep (block %d, ring wave %d of %d): %d steps, %.0f cycles/step of the sweep, waiting for blocks %.0f, for the predecessor %.0f, draining stores %.0f\n",
+                   (int)blockIdx.x, w, CH_R, nsteps, (double)((long long)__builtin_amdgcn_s_memtime() - t_begin) / nsteps, (double)t_wait / nsteps,
+                   (double)t_tag / nsteps, (double)t_drain / nsteps);
 #endif
     }
     __syncthreads();
-    return L->abort == 0; // (the code of the wait that gave up stays in L->abort for the caller's error line)
+    return ch_flag(&L->abort) == 0; // (the code of the wait that gave up stays in L->abort for the caller's error line)
+}
+
+// sum of |v[k0 + dir * s]| for s = 0 .. n-1, added to 0.0 in that order with one rounding per term -- what a step function
+// that accumulated `x1 += fabs(result)` from step to step would have got -- and their maximum.  One wave; the values are
+// final (the sweep that wrote them has returned).  64 values per load, four loads ahead of the sum; the sum itself is one
+// v_fmac_f64 per term (ch_accumulate_rows).
+__device__ __forceinline__ double ch_abs_sum_ordered(gdouble_p v, int k0, int dir, int n, double *vmax)
+{
+    const int lane = lane_id();
+    const auto ld = [&](int s0) {
+        const int s = s0 + lane;
+        return s < n ? fabs(ch_load_final(v + (k0 + dir * s))) : 0.0;
+    };
+    double acc = 0.0, mx = 0.0;
+    double a0 = ld(0), a1 = ld(64), a2 = ld(128), a3 = ld(192);
+    for (int s0 = 0; s0 < n; s0 += 64) {
+        const double cur = a0;
+        a0 = a1;
+        a1 = a2;
+        a2 = a3;
+        a3 = ld(s0 + 256);
+        mx = fmax(mx, cur);
+        const int nn = n - s0 < 64 ? n - s0 : 64;
+        for (int c = 0; c < nn; c += 16) {
+            const double rowv = __shfl(cur, c + (lane & 15));
+            acc = ch_accumulate_rows<false>(acc, rowv, nn - c < 16 ? nn - c : 16);
+        }
+    }
+    *vmax = wave_max_d(mx);
+    return acc;
 }

@@ -254,7 +254,8 @@ struct ChURows {
     }
 };
 
-#define CHAIN_THREADS 512
+#define CHAIN_THREADS 512 // CH_R ring waves, the others helpers
+static_assert(CHAIN_THREADS / 64 > CH_R, "the chain kernels need at least one helper wave");
 // blockIdx.x = chain: 0 condest(L), 1 condest(U), 2 residual test forward, 3 residual test backward.
 // Results of chains 0 and 1 go to gwork[8(m+1)], gwork[8(m+1)+1]; the work vectors (positions) stay in gwork
 // for k_stats_tail: lf = gwork[2(m+1)..], rf [3..], lb [4..], rb [5..].
@@ -275,41 +276,48 @@ __global__ void __launch_bounds__(CHAIN_THREADS) k_stats_chains(DevLU *Ds, Finis
     const bool w0 = threadIdx.x < 64;
     const int cc = blockIdx.x;
     bool ok = true;
+    // The step functions are pure (whichever ring wave has the step calls them); the 1-norms the reference accumulates
+    // from step to step are summed after the sweep, in the sweep's order (ch_abs_sum_ordered: the same additions), by wave 0,
+    // before the chain's second sweep overwrites the vector -- the other waves wait at that sweep's first barrier.
+    const auto abs_sum = [&](gdouble_p v, int k0, int dir, double *vmax) {
+#ifdef BLU_PROFILE
+        const long long t0 = (long long)__builtin_amdgcn_s_memtime();
+#endif
+        const double sum = ch_abs_sum_ordered(v, k0, dir, m, vmax);
+#ifdef BLU_PROFILE
+        if (lane == 0)
+            printf("ordered sum of |x| (block %d): %d terms, %.1f cycles/term\n", (int)blockIdx.x, m, (double)((long long)__builtin_amdgcn_s_memtime() - t0) / (m > 0 ? m : 1));
+#endif
+        return sum;
+    };
     if (cc == 0) {
         // condest(L): L' x = b with b = +-1 chosen on the fly, k descending (condest.rs:101-116), then L y = x (135-154)
-        double x1 = 0.0, xinf = 0.0, y1 = 0.0;
+        double x1 = 0.0, xinf = 0.0, y1 = 0.0, ymax;
         const ChLStage A1{D.lbeg, D.lidx, D.pinv, D.lval, nullptr};
         ok = ok && chain_sweep<false, false>(A1, L, m - 1, -1, m, wl, [&](int, bool has, double dot, double, double) {
             double temp = has ? -dot : 0.0;
             temp += temp >= 0.0 ? 1.0 : -1.0;
-            x1 += fabs(temp);
-            xinf = fmax(xinf, fabs(temp));
             return temp;
         });
+        if (w0 && ok) x1 = abs_sum(wl, m - 1, -1, &xinf);
         const ChLRows A2{R.lt_ptr, R.lt_idx, R.lt_val, D.prow, D.pinv, wl};
-        ok = ok && chain_sweep<true, true>(A2, L, 0, 1, m, wl, [&](int, bool, double acc, double, double) {
-            y1 += fabs(acc);
-            return acc;
-        });
+        ok = ok && chain_sweep<true, true>(A2, L, 0, 1, m, wl, [&](int, bool, double acc, double, double) { return acc; });
+        if (w0 && ok) y1 = abs_sum(wl, 0, 1, &ymax);
         if (w0 && lane == 0) res[0] = fmax(y1 / x1, xinf);
     } else if (cc == 1) {
         // condest(U): U' x = b, k ascending, then U y = x, k descending
-        double x1 = 0.0, xinf = 0.0, y1 = 0.0;
+        double x1 = 0.0, xinf = 0.0, y1 = 0.0, ymax;
         const ChUCols A1{(GPTR(const long long))O.u_colptr, (GPTR(const long long))O.u_rowidx, (GPTR(const double))O.u_value, nullptr};
         ok = ok && chain_sweep<false, false>(A1, L, 0, 1, m, wu, [&](int, bool has, double dot, double, double diag) {
             double temp = has ? -dot : 0.0;
             temp += temp >= 0.0 ? 1.0 : -1.0;
             temp /= diag;
-            x1 += fabs(temp);
-            xinf = fmax(xinf, fabs(temp));
             return temp;
         });
+        if (w0 && ok) x1 = abs_sum(wu, 0, 1, &xinf);
         const ChURows A2{D.ubeg, R.ur_len, R.ur_pos, R.ur_val, (GPTR(const long long))O.u_colptr, (GPTR(const double))O.u_value, wu};
-        ok = ok && chain_sweep<true, true>(A2, L, m - 1, -1, m, wu, [&](int, bool, double acc, double, double diag) {
-            const double temp = acc / diag;
-            y1 += fabs(temp);
-            return temp;
-        });
+        ok = ok && chain_sweep<true, true>(A2, L, m - 1, -1, m, wu, [&](int, bool, double acc, double, double diag) { return acc / diag; });
+        if (w0 && ok) y1 = abs_sum(wu, m - 1, -1, &ymax);
         if (w0 && lane == 0) res[1] = fmax(y1 / x1, xinf);
     } else if (cc == 2) {
         // residual test, forward system (residual_test.rs:43-66): lhs = L\rhs with rhs = +-1 on the fly, then U\lhs
@@ -333,7 +341,7 @@ __global__ void __launch_bounds__(CHAIN_THREADS) k_stats_chains(DevLU *Ds, Finis
         const ChLStage A2{D.lbeg, D.lidx, D.pinv, D.lval, lb};
         ok = ok && chain_sweep<false, false>(A2, L, m - 1, -1, m, lb, [&](int, bool has, double dot, double own, double) { return has ? own - dot : own; });
     }
-    if (!ok && threadIdx.x == 0) atomicMax(defect, L->abort ? L->abort : 99);
+    if (!ok && threadIdx.x == 0) atomicMax(defect, ch_flag(&L->abort) ? ch_flag(&L->abort) : 99);
 }
 
 // The passes over the columns and rows of B, L, U on TAIL_BLOCKS workgroups; per-workgroup maxima to the grid scratch.
@@ -379,9 +387,8 @@ __global__ void __launch_bounds__(1024) k_stats_tail_b(DevLU *Ds, FinishOut *Os,
         v[3] = fmax(v[3], stats_long_rows(D.bt_ptr, D.bt_idx, D.bt_val, D.qinv, D.pinv, D.gwork, D.m, S->rank, nlong, wave_id(), 4));
     __syncthreads();
     stats_tail_finish(D, red, chain_out, v[0], v[1], v[2], v[3]);
-    // restore the all-zero invariant of the pivot_any work area
-    const size_t ng = 7 * M1;
-    for (size_t e = threadIdx.x; e < ng; e += blockDim.x) D.gwork[e] = 0.0;
+    // the all-zero invariant of the pivot_any work area: the two result words here, the work vectors (7 (m+1) doubles) by
+    // the host's memset that follows this kernel on the stream (the clear was 0.08 of this kernel's 2.79 ms at m = 100 000)
     if (threadIdx.x < 2) D.gwork[8 * M1 + threadIdx.x] = 0.0;
 }
 
@@ -523,5 +530,5 @@ __global__ void __launch_bounds__(CHAIN_THREADS) k_solve_dense_chain(DevLU *Ds, 
         const ChSolveLStage A2{D.lbeg, D.lidx, D.pinv, D.prow, D.lval, x_out};
         ok = ok && chain_sweep<false, false>(A2, L, m - 1, -1, m, x_out, sub_dot);
     }
-    if (threadIdx.x == 0) *defect = ok ? 0 : 9100 + L->abort;
+    if (threadIdx.x == 0) *defect = ok ? 0 : 9100 + ch_flag(&L->abort);
 }
