@@ -12,6 +12,7 @@ with the same method names, argument meaning and error behaviour:
     .solve_dense_multi(rhs, trans)                 solve_dense for many right-hand sides on one handle in one call
     .solve_sparse_multi(irhs_list, xrhs_list)      solve_sparse for many right-hand sides on one handle in one call
     .get_sparse_multi(total)                       the compressed solutions the last solve_sparse_multi left in the handle
+    .maxvolume(ncol, a_p, a_i, a_x, basis, isbasic, volumetol)   maxvolume, src/maxvolume.rs:64 (one pass, in the library)
     solve_dense_batch(handles, rhs, trans)         solve_dense for many handles in one call (batch extension)
     solve_for_update_batch(handles, irhs, xrhs)    solve_for_update for many handles in one call (batch extension)
     update_batch(handles, xtbl)                    update for many handles in one call (batch extension)
@@ -46,7 +47,7 @@ EXPORTS = [
     "blu_hip_solve_sparse", "blu_hip_solve_for_update", "blu_hip_update", "blu_hip_set_skip_stats", "blu_hip_gen_lp_basis",
     "blu_hip_solve_dense_batch", "blu_hip_solve_for_update_batch", "blu_hip_update_batch",
     "blu_hip_solve_sparse_batch", "blu_hip_solve_dense_multi",
-    "blu_hip_solve_sparse_multi", "blu_hip_get_sparse_multi",
+    "blu_hip_solve_sparse_multi", "blu_hip_get_sparse_multi", "blu_hip_maxvolume",
 ]
 
 
@@ -554,6 +555,43 @@ class BLU:
             raise BluError(st, self.last_error())
         return st
 
+    # --- maxvolume (maxvolume.rs:64) ----------------------------------------------------------------
+    def maxvolume(self, ncol, a_p, a_i, a_x, basis, isbasic, volumetol):
+        """One pass of maxvolume inside the library (blu_hip_maxvolume): the decisions, results and statistics of the loop
+        blu_amd.maxvolume(self, ...) over the single entries, with the candidate columns priced in chunks on the device.
+        basis (m entries) and isbasic (ncol entries) are updated in place, lists and arrays alike.  Returns
+        (status, nupdate); ERROR_DEVICE and ERROR_OUT_OF_MEMORY raise."""
+        ap = np.ascontiguousarray(a_p, dtype=np.uint64)
+        ai = np.ascontiguousarray(a_i, dtype=np.uint64)
+        ax = np.ascontiguousarray(a_x, dtype=np.float64)
+        ncol = int(ncol)
+        if len(ap) != ncol + 1 or len(basis) != self.m or len(isbasic) != ncol or len(ai) != len(ax) or (ncol >= 0 and len(ai) < int(ap[-1])):
+            raise ValueError("maxvolume: a_p needs ncol + 1 entries, basis m, isbasic ncol, a_i / a_x a_p[ncol]")
+        b = np.array(basis, dtype=np.int64)
+        ib = np.array(isbasic, dtype=np.int64)
+        nup = C.c_int64(0)
+        L = lib()
+        L.blu_hip_maxvolume.argtypes = [C.c_void_p, C.c_int64] + [C.c_void_p] * 5 + [C.c_double, C.c_void_p]
+        st = L.blu_hip_maxvolume(self._h, ncol, ap.ctypes.data, ai.ctypes.data if len(ai) else None, ax.ctypes.data if len(ax) else None,
+                                 b.ctypes.data or 8, ib.ctypes.data or 8, float(volumetol), C.addressof(nup))
+        basis[:] = b.tolist() if isinstance(basis, list) else b
+        isbasic[:] = ib.tolist() if isinstance(isbasic, list) else ib
+        if st in (K.ERROR_DEVICE, K.ERROR_OUT_OF_MEMORY):
+            raise BluError(st, self.last_error())
+        return st, int(nup.value)
+
+    def dbg_set_maxvolume_chunk(self, n):
+        """Candidates per chunk of maxvolume (n <= 0: the policy); results do not depend on it."""
+        lib().blu_hip_dbg_set_maxvolume_chunk.argtypes = [C.c_void_p, C.c_int64]
+        lib().blu_hip_dbg_set_maxvolume_chunk(self._h, int(n))
+
+    def dbg_maxvolume_counts(self):
+        """The last maxvolume pass: (chunks launched, candidates priced, candidates discarded behind a hit, hits)."""
+        out = (C.c_int64 * 4)()
+        lib().blu_hip_dbg_maxvolume_counts.argtypes = [C.c_void_p, C.c_void_p]
+        lib().blu_hip_dbg_maxvolume_counts(self._h, out)
+        return tuple(int(x) for x in out)
+
     # --- test hooks (step-wise comparison with the oracle) -------------------------------------------
     def dbg_set_stop(self, n):
         lib().blu_hip_dbg_set_stop(self._h, int(n))
@@ -572,6 +610,12 @@ class BLU:
         """Arena slack of the update path (entries); small values force the host-side growth loop."""
         lib().blu_hip_dbg_set_upd_extra.argtypes = [C.c_void_p, C.c_int64]
         lib().blu_hip_dbg_set_upd_extra(self._h, int(n))
+
+    def dbg_upd_grows(self):
+        """Storage requests of the update kernels this handle has answered so far."""
+        lib().blu_hip_dbg_upd_grows.restype = C.c_int64
+        lib().blu_hip_dbg_upd_grows.argtypes = [C.c_void_p]
+        return int(lib().blu_hip_dbg_upd_grows(self._h))
 
     def dbg_set_multi_ws_bytes(self, n):
         """Byte limit of the work vectors plus staging block of solve_dense_multi (-1: the default, 1 GiB); small values

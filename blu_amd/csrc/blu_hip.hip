@@ -91,6 +91,7 @@ struct blu_hip {
     int64_t upd_alloc_m;    // m the fixed-size arrays of uw were allocated for (-1: none)
     int64_t upd_for_nfact;  // nfactorize uw was built for (-1: none)
     int64_t upd_extra;      // debug: arena slack of the update path (-1: default)
+    int64_t upd_grows;      // debug: storage requests of the update kernels answered so far
     // blu_hip_solve_dense_multi (blu_solve_multi.inc): one work vector per right-hand side in flight, and the staging block of
     // host inputs; allocated at the first call, grown on demand
     double *mws, *mio;
@@ -112,6 +113,18 @@ struct blu_hip {
     bool sm_have;                // a result is held
     std::vector<int64_t> sm_ilhs;
     std::vector<double> sm_xlhs;
+    // blu_hip_maxvolume (blu_maxvolume.inc): A resident on the device for the pass -- column offsets, row indices as
+    // 64-bit (blu_hip_factorize_device) and as int (the solves), values --, the columns of a chunk and the pick record
+    long long *mv_ap;
+    unsigned long long *mv_ai64;
+    int *mv_ai;
+    double *mv_ax;
+    int64_t mv_pcap, mv_nzcap;   // entries mv_ap / the three arrays of A hold
+    int *mv_cols;
+    int64_t mv_colscap;
+    long long *mv_rec;
+    int64_t mv_chunk;            // debug: fixed chunk size (<= 0: the policy)
+    int64_t mv_counts[4];        // last pass: chunks launched, candidates priced, candidates discarded behind a hit, hits
     int64_t sp_l_flops, sp_u_flops; // lu.l_flops / lu.u_flops
     int sp_branch;                  // 1 sparse, 2 sequential: branch of the last solve_sparse (diagnostic)
     // timing
@@ -181,6 +194,7 @@ static const int64_t kIntMax = 0x7ffffff0;
 static void free_upd(blu_hip *h);
 static void free_multi(blu_hip *h);
 static void free_sparse_multi(blu_hip *h);
+static void free_maxvolume(blu_hip *h);
 static void free_all(blu_hip *h)
 {
     DevLU &D = h->D;
@@ -199,6 +213,7 @@ static void free_all(blu_hip *h)
     free_upd(h);
     free_multi(h);
     free_sparse_multi(h);
+    free_maxvolume(h);
     // everything else lives in the slab
     dfree(h->slab);
 }
@@ -283,6 +298,7 @@ extern "C" blu_hip *blu_hip_new(int64_t m, int64_t b_nz, int device)
     h->upd_alloc_m = -1;
     h->upd_for_nfact = -1;
     h->upd_extra = -1;
+    h->upd_grows = 0;
     h->mws = h->mio = nullptr;
     h->mws_cols = h->mio_cols = 0;
     h->multi_ws_bytes = -1;
@@ -298,6 +314,16 @@ extern "C" blu_hip *blu_hip_new(int64_t m, int64_t b_nz, int device)
     h->sm_ws_bytes = -1;
     h->sm_last_chunk = 0;
     h->sm_have = false;
+    h->mv_ap = nullptr;
+    h->mv_ai64 = nullptr;
+    h->mv_ai = nullptr;
+    h->mv_ax = nullptr;
+    h->mv_pcap = h->mv_nzcap = 0;
+    h->mv_cols = nullptr;
+    h->mv_colscap = 0;
+    h->mv_rec = nullptr;
+    h->mv_chunk = 0;
+    memset(h->mv_counts, 0, sizeof h->mv_counts);
     h->chain_ok = 0;
     h->chain_defects = 0;
     h->ur_len = h->ur_pos = nullptr;
@@ -943,6 +969,7 @@ extern "C" int blu_hip_solve_dense(blu_hip *h, const double *rhs, double *lhs, c
 #include "blu_update_batch.inc"
 #include "blu_solve_sparse_batch.inc"
 #include "blu_solve_sparse_multi.inc"
+#include "blu_maxvolume.inc"
 
 // solve_sparse -- src/solve_sparse.rs:36-68, lu/solve_sparse.rs:11-360 (fresh factorization: nforrest == 0)
 extern "C" int blu_hip_solve_sparse(blu_hip *h, int64_t nzrhs, const uint64_t *irhs, const double *xrhs, int64_t *p_nzlhs,

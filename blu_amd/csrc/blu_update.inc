@@ -87,6 +87,7 @@ static int ensure_upd(blu_hip *h)
 // answer a storage request of the update kernels (the device counterpart of lu_realloc_obj, blu.rs:345-377)
 static int grow_upd(blu_hip *h)
 {
+    h->upd_grows++;
     UpdWs &U = h->uw;
     const UpdState &s = h->ust;
     if (s.status == UPD_NEED_R) {
@@ -168,14 +169,15 @@ static int fetch_solution(blu_hip *h, int64_t *p_nzlhs, int64_t *ilhs, double *l
     return BLU_OK;
 }
 
-// one launch of k_solve_upd with the storage-request loop around it
-static int run_solve_upd(blu_hip *h, int mode, int want, int64_t nzrhs, int tr)
+// one launch of k_solve_upd with the storage-request loop around it; the right-hand side is on the device already
+// (h->d_irhs / h->d_xrhs after upload_rhs, or a column of the resident A of blu_hip_maxvolume)
+static int run_solve_upd(blu_hip *h, int mode, int want, int64_t nzrhs, int tr, const int *d_irhs, const double *d_xrhs)
 {
     const int nz_sparse = (int)(h->sparse_thres * (double)h->m);
     for (int attempt = 0; attempt < 64; attempt++) {
         int st = marker_room(h);
         if (st != BLU_OK) return st;
-        hipLaunchKernelGGL(k_solve_upd, dim3(1), dim3(64), 0, h->stream, h->dD, h->sw, h->uw, mode, want, (int)nzrhs, h->d_irhs, h->d_xrhs, tr,
+        hipLaunchKernelGGL(k_solve_upd, dim3(1), dim3(64), 0, h->stream, h->dD, h->sw, h->uw, mode, want, (int)nzrhs, d_irhs, d_xrhs, tr,
                            h->marker, nz_sparse);
         if (!hip_ok(h, hipStreamSynchronize(h->stream), "k_solve_upd")) return BLU_ERROR_DEVICE;
         h->marker += 4;
@@ -220,7 +222,7 @@ extern "C" int blu_hip_solve_for_update(blu_hip *h, int64_t nzrhs, const uint64_
     if (want) *p_nzlhs = 0;
     st = upload_rhs(h, tr ? 1 : nzrhs, irhs, tr ? nullptr : xrhs);
     if (st != BLU_OK) return st;
-    st = run_solve_upd(h, 1, want, tr ? 1 : nzrhs, tr);
+    st = run_solve_upd(h, 1, want, tr ? 1 : nzrhs, tr, h->d_irhs, h->d_xrhs);
     if (st != BLU_OK) return st;
     return fetch_solution(h, p_nzlhs, ilhs, lhs);
 }
@@ -265,7 +267,7 @@ static int solve_sparse_updated(blu_hip *h, int64_t nzrhs, const uint64_t *irhs,
     if (st != BLU_OK) return st;
     st = upload_rhs(h, nzrhs, irhs, xrhs);
     if (st != BLU_OK) return st;
-    st = run_solve_upd(h, 0, 1, nzrhs, tr);
+    st = run_solve_upd(h, 0, 1, nzrhs, tr, h->d_irhs, h->d_xrhs);
     if (st != BLU_OK) return st;
     return fetch_solution(h, p_nzlhs, ilhs, lhs);
 }
@@ -290,3 +292,5 @@ extern "C" int blu_hip_dbg_set_upd_extra(blu_hip *h, int64_t extra)
     h->upd_for_nfact = -1;
     return BLU_OK;
 }
+// storage requests of the update kernels this handle has answered so far (tests: the knob above did force some)
+extern "C" int64_t blu_hip_dbg_upd_grows(const blu_hip *h) { return h ? h->upd_grows : 0; }

@@ -1229,3 +1229,122 @@ __global__ void __launch_bounds__(64) k_upd_add_flops(UpdWs U, long long l_flops
         st->update_cost_numer += (double)r_flops;
     }
 }
+
+// ---------------------------------------------------------------------------------------------------------
+// blu_hip_maxvolume (blu_maxvolume.inc): a chunk of candidate columns of the resident A priced at once.  A forward
+// solve_for_update with a solution differs from the mode-0 solve in two things only -- it stores the spike and sets
+// ftran_for -- so the candidates run the body of k_solve_upd_multi: slot blockIdx.x of the pool, the handle's one UpdWs
+// (read only), the counters left in the slot.  k_price_pick then counts what the loop of single calls would have counted:
+// the candidates in front of the first one that is taken or refused.
+// ---------------------------------------------------------------------------------------------------------
+struct PriceA {
+    const long long *ap; // column offsets
+    const int *ai;       // row indices (one that does not fit an int is stored as 0x7fffffff: never below m)
+    const double *ax;
+};
+// W.out[5] imax, [6] the bits of xtbl, [7] 1: the column has more than m entries or an index >= m (nothing was solved)
+__global__ void __launch_bounds__(64) k_price_multi(const DevLU *Ds, SparseSlots P, SparseWs H, UpdWs U, PriceA A, const int *cols, int marker,
+                                                    int nz_sparse)
+{
+    __shared__ DfsRing dfs_ring;
+    const long long s = blockIdx.x;
+    const SparseWs W = slot_ws(P, H, s);
+    const DevG D(Ds[0]);
+    const int lane = lane_id(), m = D.m;
+    const int j = cols[s];
+    const long long b = A.ap[j], e = A.ap[j + 1];
+    bool bad = e - b > m;
+    if (!bad) {
+        for (long long q = b + lane; q < e; q += 64) bad = bad || (unsigned)A.ai[q] >= (unsigned)m;
+        bad = __ballot(bad) != 0;
+    }
+    if (bad) {
+        (void)slot_skipped(W, -1);
+        if (lane == 0) {
+            W.out[5] = 0;
+            W.out[6] = 0;
+            W.out[7] = 1;
+        }
+        return;
+    }
+    solve_upd_wave<false>(D, W, U, 0, 1, (int)(e - b), A.ai + b, A.ax + b, 0, marker, nz_sparse, &dfs_ring);
+    wave_mem_sync();
+    // the scan of maxvolume.rs:121-131: the first entry in pattern order with the largest |x| (strict >, from 0.0: a NaN
+    // is never taken, an empty or all-zero solution gives xtbl = 0, imax = 0)
+    const int nz = (int)W.out[0];
+    double best = 0.0;
+    int bpos = 0x7fffffff;
+    for (int n = lane; n < nz; n += 64) {
+        const double a = fabs(W.xval[n]);
+        if (a > best) {
+            best = a;
+            bpos = n;
+        }
+    }
+    const double xmax = wave_max_d(best);
+    const int pos = wave_min_i(best == xmax && xmax > 0.0 ? bpos : 0x7fffffff);
+    if (lane == 0) {
+        long long bits = 0, imax = 0; // (+0.0)
+        if (pos != 0x7fffffff) {
+            const double xtbl = W.xval[pos];
+            memcpy(&bits, &xtbl, sizeof bits);
+            imax = W.ilhs[pos];
+        }
+        W.out[5] = imax;
+        W.out[6] = bits;
+        W.out[7] = 0;
+    }
+}
+// One wave over the nc slot records in order.  rec[0] kind (0 no event, 1 candidate taken, 2 column refused) + 256 * branch
+// of the last counted candidate (0: none counted), [1] position of the event in the chunk, [2] its column, [3] imax,
+// [4] bits of xtbl, [5..7] l / u / r_flops summed over the positions in front of the event (all nc without one).  The
+// sums go into the shared UpdState as k_upd_add_flops adds them.
+__global__ void __launch_bounds__(64) k_price_pick(SparseSlots P, UpdWs U, const int *cols, int nc, double volumetol, long long *rec)
+{
+    const int lane = lane_id();
+    long long l_flops = 0, u_flops = 0, r_flops = 0;
+    int kind = 0, pos = nc, branch = 0;
+    for (int c0 = 0; c0 < nc && kind == 0; c0 += 64) {
+        const int s = c0 + lane;
+        const bool valid = s < nc;
+        const long long *o = P.out + 8 * (long long)(valid ? s : c0);
+        const bool refused = valid && o[7] != 0;
+        double xtbl;
+        const long long bits = o[6];
+        memcpy(&xtbl, &bits, sizeof xtbl);
+        const bool taken = valid && !refused && !(fabs(xtbl) <= volumetol); // maxvolume.rs:134 (a NaN tolerance takes every column)
+        const unsigned long long ev = __ballot(refused || taken), rf = __ballot(refused);
+        const int first = ev ? __ffsll((long long)ev) - 1 : 64;
+        if (valid && lane < first) {
+            l_flops += o[1];
+            u_flops += o[2];
+            r_flops += o[4];
+        }
+        const int ncounted = min(first, nc - c0);
+        if (ncounted > 0) branch = (int)P.out[8 * (long long)(c0 + ncounted - 1) + 3];
+        if (ev) {
+            kind = ((rf >> first) & 1) ? 2 : 1;
+            pos = c0 + first;
+        }
+    }
+    l_flops = wave_sum_ll(l_flops);
+    u_flops = wave_sum_ll(u_flops);
+    r_flops = wave_sum_ll(r_flops);
+    if (lane == 0) {
+        UpdState *st = U.st;
+        st->status = UPD_OK;
+        st->l_flops += l_flops;
+        st->u_flops += u_flops;
+        st->r_flops += r_flops;
+        st->update_cost_numer += (double)r_flops;
+        const long long *o = P.out + 8 * (long long)(kind ? pos : 0);
+        rec[0] = kind + 256 * branch;
+        rec[1] = pos;
+        rec[2] = kind ? cols[pos] : -1;
+        rec[3] = kind == 1 ? o[5] : 0;
+        rec[4] = kind == 1 ? o[6] : 0;
+        rec[5] = l_flops;
+        rec[6] = u_flops;
+        rec[7] = r_flops;
+    }
+}

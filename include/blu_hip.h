@@ -338,6 +338,32 @@ int blu_hip_solve_sparse_multi(blu_hip *h, int64_t nrhs, const int64_t *rhs_ptr,
  * or for NULL arrays while the held total is above 0. */
 int blu_hip_get_sparse_multi(blu_hip *h, int64_t *ilhs, double *xlhs);
 
+/* maxvolume -- src/maxvolume.rs:64-224: one pass over the columns of the rectangular A (compressed columns a_p[ncol + 1],
+ * a_i, a_x; ncol >= m), which pivots every non-basic column into the basis that grows |det B| by more than volumetol.
+ * basis[m] holds the column indices of the start basis and isbasic[ncol] is nonzero exactly for them; both are updated in
+ * place.  *p_nupdate (may be NULL) gets the number of basis changes; a caller repeats the pass until it is 0.
+ * The pass is, decision for decision, the reference's loop over blu_hip_factorize, blu_hip_solve_for_update (forward with
+ * the solution, then transposed) and blu_hip_update on this handle, with its refactorization rule (eta file full, pivot
+ * error above 1e-8, BLU_STAT_UPDATE_COST above 1): the same status, *p_nupdate, basis and isbasic -- also after a pass
+ * that ends early with an error --, and afterwards the same statistics (NUPDATE, NFACTORIZE, NFORREST, PIVOT_ERROR,
+ * L / U / R_FLOPS, R_NZ, U_NZ, MAX_ETA, UPDATE_COST, the permutation totals, the branch statistic) and the same bits from
+ * every later call -- with one exception: the loop's last forward blu_hip_solve_for_update, of a column that was not
+ * taken, leaves a pending spike behind, so that a transposed blu_hip_solve_for_update and blu_hip_update right after the
+ * loop would insert that column; the pass prices without storing spikes, and there blu_hip_update answers
+ * BLU_ERROR_INVALID_CALL until the caller has made a forward blu_hip_solve_for_update of its own.
+ * Checked before anything is touched: NULL h, a_p, basis or isbasic BLU_ERROR_ARGUMENT_MISSING; ncol < 0 or a decreasing
+ * a_p BLU_ERROR_INVALID_ARGUMENT; NULL a_i or a_x while A has entries BLU_ERROR_ARGUMENT_MISSING; a basis[i] outside
+ * [0, ncol) BLU_ERROR_INVALID_ARGUMENT; volumetol < 1.0 BLU_ERROR_INVALID_ARGUMENT with *p_nupdate = 0.
+ * A candidate column with an index >= m or more than m entries ends the pass with BLU_ERROR_INVALID_ARGUMENT when its
+ * turn comes; BLU_WARNING_SINGULAR_MATRIX or an error of a factorization, a solve or the update ends it with that status.
+ * A is uploaded once per pass into buffers the handle keeps (20 bytes per entry).  The candidates are priced in chunks,
+ * one wave each on the workspace pool of blu_hip_solve_sparse_multi (k_price_multi), and one wave picks the first
+ * candidate taken or refused and counts those in front of it (k_price_pick): per chunk one small upload, two launches,
+ * one synchronize and a 64-byte download.  A candidate that is taken is solved again through the single path, which
+ * stores the spike; what was priced behind it is priced again against the new factors. */
+int blu_hip_maxvolume(blu_hip *h, int64_t ncol, const uint64_t *a_p, const uint64_t *a_i, const double *a_x,
+                      int64_t *basis, int64_t *isbasic, double volumetol, int64_t *p_nupdate);
+
 /* factorize() ends with the statistics tail of src/factorize.rs:121-147 (condest(L), condest(U),
  * residual_test; getters BLU_STAT_CONDEST_* .. BLU_STAT_RESIDUAL_TEST).  It is a chain of 8 triangular
  * sweeps (~17 % of the factorize time at 100k); a caller that never reads those getters can switch

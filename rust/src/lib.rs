@@ -84,6 +84,10 @@ extern "C" {
         status: *mut c_int,
     ) -> c_int;
     fn blu_hip_get_sparse_multi(h: *mut BluHip, ilhs: *mut i64, xlhs: *mut f64) -> c_int;
+    fn blu_hip_maxvolume(
+        h: *mut BluHip, ncol: i64, a_p: *const u64, a_i: *const u64, a_x: *const f64, basis: *mut i64, isbasic: *mut i64, volumetol: f64,
+        p_nupdate: *mut i64,
+    ) -> c_int;
     fn blu_hip_last_error(h: *const BluHip) -> *const c_char;
 }
 
@@ -375,6 +379,36 @@ impl BLU {
             ilhs.iter().map(|&i| i as usize).collect(),
             xlhs,
         ))
+    }
+
+    /// One pass of `maxvolume` (`src/maxvolume.rs:64-224`) inside the library: the decisions, results and statistics of
+    /// `crate::maxvolume(self, ...)`, the loop over `factorize` / `solve_for_update` / `update`, with the candidate columns
+    /// priced in chunks on the device.  `basis` (`m` entries) and `isbasic` (`ncol` entries) are updated in place;
+    /// `p_nupdate` is written on every exit the C entry writes it on.
+    #[allow(clippy::too_many_arguments)]
+    pub fn maxvolume(
+        &mut self, ncol: usize, a_p: &[usize], a_i: &[usize], a_x: &[f64], basis: &mut [LUInt], isbasic: &mut [LUInt], volumetol: f64,
+        p_nupdate: Option<&mut LUInt>,
+    ) -> Result<(), Status> {
+        // the C side reads a_p[0..=ncol], a_i / a_x[a_p[0]..a_p[ncol]), basis[0..m) and isbasic[0..ncol): never hand it less
+        if a_p.len() != ncol + 1 || basis.len() != self.m || isbasic.len() != ncol || a_p.windows(2).any(|w| w[1] < w[0]) {
+            return Err(Status::ErrorInvalidArgument);
+        }
+        if a_p[ncol] > a_i.len() || a_p[ncol] > a_x.len() {
+            return Err(Status::ErrorInvalidArgument);
+        }
+        let mut nupdate: i64 = 0;
+        let wants = p_nupdate.is_some();
+        let code = unsafe {
+            blu_hip_maxvolume(
+                self.lu.h, ncol as i64, a_p.as_ptr() as *const u64, a_i.as_ptr() as *const u64, a_x.as_ptr(), basis.as_mut_ptr(),
+                isbasic.as_mut_ptr(), volumetol, if wants { &mut nupdate } else { std::ptr::null_mut() },
+            )
+        };
+        if let Some(p) = p_nupdate {
+            *p = nupdate;
+        }
+        status_of(code)
     }
 
     // lu_clear_lhs, blu.rs:380-395

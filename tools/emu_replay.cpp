@@ -25,6 +25,10 @@
 //               blu_hip_solve_sparse_multi with host arrays built here that end with their last entry (tot = rhs_ptr[nrhs],
 //               total = lhs_ptr[nrhs]; rhs_ptr[0] = 0), then blu_hip_get_sparse_multi into arrays of exactly total entries
 //   OP_SPARSE_MULTI_GET total ilhs[total] xlhs[total]       blu_hip_get_sparse_multi twice: the held result, both times
+//   OP_MAXVOLUME_CHUNK n                                    blu_hip_dbg_set_maxvolume_chunk(n): candidates per chunk of the next passes
+//   OP_MAXVOLUME ncol a_p[ncol + 1] a_i[nnz] a_x[nnz] basis[m] isbasic[ncol] volumetol(double) with_nupdate status nupdate
+//               basis[m] isbasic[ncol]                      blu_hip_maxvolume with host arrays built here that end with their last
+//               entry (nnz = a_p[ncol], a_p[0] = 0); with_nupdate == 0 passes a NULL p_nupdate and nupdate is not compared
 //   OP_END
 #include "../include/blu_hip.h"
 
@@ -39,13 +43,16 @@ extern "C" int blu_hip_dbg_set_upd_extra(blu_hip *h, int64_t extra);
 extern "C" int blu_hip_dbg_set_multi_ws_bytes(blu_hip *h, int64_t bytes);
 // ... and of blu_hip_solve_sparse_multi (blu_solve_sparse_multi.inc)
 extern "C" int blu_hip_dbg_set_sparse_multi_ws_bytes(blu_hip *h, int64_t bytes);
+// ... and of blu_hip_maxvolume (blu_maxvolume.inc)
+extern "C" int blu_hip_dbg_set_maxvolume_chunk(blu_hip *h, int64_t n);
 
 enum { OP_END = 0, OP_NEW, OP_EXTRA, OP_PARAM, OP_FACT, OP_DENSE, OP_SPARSE, OP_FORUPD, OP_UPDATE, OP_STAT, OP_MULTI_WS, OP_DENSE_MULTI,
-       OP_SPARSE_MULTI_WS, OP_SPARSE_MULTI, OP_SPARSE_MULTI_GET };
+       OP_SPARSE_MULTI_WS, OP_SPARSE_MULTI, OP_SPARSE_MULTI_GET, OP_MAXVOLUME, OP_MAXVOLUME_CHUNK };
 static const int64_t TAPE_MAGIC = 0x3145504154554c42LL; // "BLUTAPE1"
 static const char *const OP_NAME[] = {"end", "new", "dbg_set_upd_extra", "set_param", "factorize", "solve_dense", "solve_sparse",
                                       "solve_for_update", "update", "get_stat", "dbg_set_multi_ws_bytes", "solve_dense_multi",
-                                      "dbg_set_sparse_multi_ws_bytes", "solve_sparse_multi", "get_sparse_multi"};
+                                      "dbg_set_sparse_multi_ws_bytes", "solve_sparse_multi", "get_sparse_multi", "maxvolume",
+                                      "dbg_set_maxvolume_chunk"};
 
 static std::vector<int64_t> tape;
 static size_t pos = 0;
@@ -130,7 +137,7 @@ int main(int argc, char **argv)
     int64_t m = 0;
     for (;;) {
         op = word();
-        if (op < OP_END || op > OP_SPARSE_MULTI_GET) {
+        if (op < OP_END || op > OP_MAXVOLUME_CHUNK) {
             fprintf(stderr, "emu_replay: unknown record %lld after call %ld\n", (long long)op, ncall);
             return 2;
         }
@@ -266,6 +273,35 @@ int main(int argc, char **argv)
                 same_words("ilhs", ilhs.data(), wi, total, false);
                 same_words("xlhs", xlhs.data(), wx, total, true);
             }
+            break;
+        }
+        case OP_MAXVOLUME_CHUNK:
+            same_int("status", blu_hip_dbg_set_maxvolume_chunk(h, word()), BLU_OK);
+            break;
+        case OP_MAXVOLUME: {
+            const size_t ncol = (size_t)word(), M = (size_t)m;
+            const uint64_t *p = (const uint64_t *)take(ncol + 1);
+            const size_t nnz = (size_t)p[ncol];
+            // (copies that end with their last entry: an access behind them is an AddressSanitizer report)
+            std::vector<uint64_t> a_p(p, p + ncol + 1);
+            const uint64_t *ti = (const uint64_t *)take(nnz);
+            std::vector<uint64_t> a_i(ti, ti + nnz);
+            const double *tx = (const double *)take(nnz);
+            std::vector<double> a_x(tx, tx + nnz);
+            const int64_t *tb = take(M);
+            std::vector<int64_t> basis(tb, tb + M);
+            const int64_t *tn = take(ncol);
+            std::vector<int64_t> isbasic(tn, tn + ncol);
+            const double volumetol = real();
+            const bool with_nupdate = word() != 0;
+            int64_t nupdate = -1;
+            const int st = blu_hip_maxvolume(h, (int64_t)ncol, a_p.data(), nnz ? a_i.data() : nullptr, nnz ? a_x.data() : nullptr, basis.data(),
+                                             isbasic.data(), volumetol, with_nupdate ? &nupdate : nullptr);
+            same_int("status", st, word());
+            const int64_t want_nupdate = word();
+            if (with_nupdate) same_int("nupdate", nupdate, want_nupdate);
+            same_words("basis", basis.data(), take(M), M, false);
+            same_words("isbasic", isbasic.data(), take(ncol), ncol, false);
             break;
         }
         case OP_STAT: {
