@@ -17,6 +17,8 @@ with the same method names, argument meaning and error behaviour:
     solve_for_update_batch(handles, irhs, xrhs)    solve_for_update for many handles in one call (batch extension)
     update_batch(handles, xtbl)                    update for many handles in one call (batch extension)
     solve_sparse_batch(handles, irhs, xrhs)        solve_sparse for many handles in one call (batch extension)
+    .clone()                                       a new BLU holding this one's complete state (blu_hip_clone)
+    copy_batch(src, dsts)                          the state of one handle copied into many in one launch (batch extension)
     .set_param / .stat                             pub fields / getters     lu.rs:11-66, 398-684
 
 There is NO CPU fallback: if the shared library is missing, or no gfx950 device is visible, this
@@ -48,6 +50,7 @@ EXPORTS = [
     "blu_hip_solve_dense_batch", "blu_hip_solve_for_update_batch", "blu_hip_update_batch",
     "blu_hip_solve_sparse_batch", "blu_hip_solve_dense_multi",
     "blu_hip_solve_sparse_multi", "blu_hip_get_sparse_multi", "blu_hip_maxvolume",
+    "blu_hip_copy_batch", "blu_hip_clone",
 ]
 
 
@@ -333,6 +336,29 @@ def solve_sparse_batch(handles, irhs, xrhs, trans="N"):
     return out
 
 
+def copy_batch(src, dsts):
+    """The complete logical state of `src` copied into every handle of `dsts` (same m, same device) in one launch: each
+    is afterwards observably src -- parameters, statistics, a pending solve_for_update, the bits of every later call -- and
+    independent of it.  The Python-side solution of a destination (lhs / ilhs / nzlhs) is cleared.  Returns the per-member
+    statuses.  A refused call raises BluError, as does ERROR_DEVICE or ERROR_OUT_OF_MEMORY of a member."""
+    n = len(dsts)
+    L = lib()
+    L.blu_hip_copy_batch.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p]
+    N = max(n, 1)
+    hs = (C.c_void_p * N)(*[h._h for h in dsts])
+    st = (C.c_int * N)()
+    rc = L.blu_hip_copy_batch(src._h, hs, n, st)
+    if rc in (K.ERROR_ARGUMENT_MISSING, K.ERROR_INVALID_ARGUMENT):  # (codes only a refusal of the whole call returns)
+        raise BluError(rc, "copy_batch refused")
+    out = [int(s) for s in st][:n]
+    for h, s in zip(dsts, out):
+        if s in (K.ERROR_DEVICE, K.ERROR_OUT_OF_MEMORY):
+            raise BluError(s, h.last_error() or src.last_error())
+        h.lhs = h.ilhs = None
+        h.nzlhs = 0
+    return out
+
+
 class BLU:
     """`struct BLU` (src/blu.rs:9-20) backed by the HIP implementation."""
 
@@ -352,6 +378,31 @@ class BLU:
 
     def __del__(self):
         self.close()
+
+    def clone(self):
+        """A new BLU with the complete logical state of this one (blu_hip_clone: blu_hip_new with this handle's size hint
+        and device, then the copy).  lhs / ilhs / nzlhs are not carried over."""
+        L = lib()
+        L.blu_hip_clone.restype = C.c_void_p
+        L.blu_hip_clone.argtypes = [C.c_void_p]
+        h = L.blu_hip_clone(self._h)
+        if not h:
+            raise BluError(K.ERROR_DEVICE, "blu_hip_clone failed (out of memory or device error) " + self.last_error())
+        c = BLU.__new__(BLU)
+        c.m = self.m
+        c.device = self.device
+        c.lhs = c.ilhs = None
+        c.nzlhs = 0
+        c._h = h
+        return c
+
+    def dbg_copy_counts(self):
+        """The last copy_batch / clone with this handle as the source: (kernel launches, synchronizes, host-to-device
+        copies, device allocations made, bytes of state read per destination, bytes written to all destinations)."""
+        out = (C.c_int64 * 6)()
+        lib().blu_hip_dbg_copy_counts.argtypes = [C.c_void_p, C.c_void_p]
+        lib().blu_hip_dbg_copy_counts(self._h, out)
+        return tuple(int(x) for x in out)
 
     # --- parameters / statistics (lu.rs public fields and getters) -------------------------------
     def set_param(self, key, value):

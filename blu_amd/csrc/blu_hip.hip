@@ -43,6 +43,7 @@ using pv_wave2::k_pivot_loop_wave2_r3;
 #include "k_stats.hip"
 #include "k_chain.hip"
 #include "k_update.hip"
+#include "k_copy.hip"
 
 #define BLU_STOPPED_STATUS 100 /* debug stepping only */
 
@@ -125,6 +126,11 @@ struct blu_hip {
     long long *mv_rec;
     int64_t mv_chunk;            // debug: fixed chunk size (<= 0: the policy)
     int64_t mv_counts[4];        // last pass: chunks launched, candidates priced, candidates discarded behind a hit, hits
+    // blu_hip_copy_batch (blu_copy.inc) with this handle as the source: the staging block on the device (segment table,
+    // destination pointers, the destinations' descriptors), kept for the next call, and the counts of the last call
+    char *cp_stage;
+    size_t cp_stage_cap;
+    int64_t cp_counts[6];
     int64_t sp_l_flops, sp_u_flops; // lu.l_flops / lu.u_flops
     int sp_branch;                  // 1 sparse, 2 sequential: branch of the last solve_sparse (diagnostic)
     // timing
@@ -166,9 +172,11 @@ static bool hip_ok(blu_hip *h, hipError_t e, const char *what)
         if (!hip_ok((h), (call), #call)) return false;  \
     } while (0)
 
+static thread_local int64_t t_dalloc_calls = 0; // device allocations asked for by this thread (blu_hip_dbg_copy_counts)
 template <class T> static bool dalloc(blu_hip *h, T **p, size_t n)
 {
     *p = nullptr;
+    t_dalloc_calls++;
     return hip_ok(h, hipMalloc((void **)p, std::max<size_t>(n, 1) * sizeof(T)), "hipMalloc");
 }
 template <class T> static void dfree(T *&p)
@@ -214,6 +222,7 @@ static void free_all(blu_hip *h)
     free_multi(h);
     free_sparse_multi(h);
     free_maxvolume(h);
+    dfree(h->cp_stage);
     // everything else lives in the slab
     dfree(h->slab);
 }
@@ -324,6 +333,9 @@ extern "C" blu_hip *blu_hip_new(int64_t m, int64_t b_nz, int device)
     h->mv_rec = nullptr;
     h->mv_chunk = 0;
     memset(h->mv_counts, 0, sizeof h->mv_counts);
+    h->cp_stage = nullptr;
+    h->cp_stage_cap = 0;
+    memset(h->cp_counts, 0, sizeof h->cp_counts);
     h->chain_ok = 0;
     h->chain_defects = 0;
     h->ur_len = h->ur_pos = nullptr;
@@ -970,6 +982,7 @@ extern "C" int blu_hip_solve_dense(blu_hip *h, const double *rhs, double *lhs, c
 #include "blu_solve_sparse_batch.inc"
 #include "blu_solve_sparse_multi.inc"
 #include "blu_maxvolume.inc"
+#include "blu_copy.inc"
 
 // solve_sparse -- src/solve_sparse.rs:36-68, lu/solve_sparse.rs:11-360 (fresh factorization: nforrest == 0)
 extern "C" int blu_hip_solve_sparse(blu_hip *h, int64_t nzrhs, const uint64_t *irhs, const double *xrhs, int64_t *p_nzlhs,

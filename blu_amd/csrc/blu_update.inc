@@ -22,8 +22,8 @@ static bool download_upd(blu_hip *h)
     return hip_ok(h, hipMemcpy(&h->ust, h->uw.st, sizeof(UpdState), hipMemcpyDeviceToHost), "d2h update state");
 }
 
-// room for the mutable copies of U, the maps, the pivot sequence and the eta file of THIS factorization
-static int ensure_upd_ws(blu_hip *h)
+// the fixed-size (m-dependent) arrays of the update workspace
+static int ensure_upd_fixed(blu_hip *h)
 {
     UpdWs &U = h->uw;
     const size_t M = (size_t)h->m;
@@ -37,6 +37,18 @@ static int ensure_upd_ws(blu_hip *h)
         if (!a) return BLU_ERROR_OUT_OF_MEMORY;
         U.wcapacity = U.uccapacity = U.rcapacity = 0;
         h->upd_alloc_m = h->m;
+    }
+    return BLU_OK;
+}
+
+// room for the mutable copies of U, the maps, the pivot sequence and the eta file of THIS factorization
+static int ensure_upd_ws(blu_hip *h)
+{
+    UpdWs &U = h->uw;
+    const size_t M = (size_t)h->m;
+    {
+        const int st = ensure_upd_fixed(h);
+        if (st != BLU_OK) return st;
     }
     // arenas: what build_factors asks for (build_factors.rs:160-177) plus room for a few hundred updates
     const int64_t u_nz = h->hs.u_nz;

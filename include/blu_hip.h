@@ -364,6 +364,41 @@ int blu_hip_get_sparse_multi(blu_hip *h, int64_t *ilhs, double *xlhs);
 int blu_hip_maxvolume(blu_hip *h, int64_t ncol, const uint64_t *a_p, const uint64_t *a_i, const double *a_x,
                       int64_t *basis, int64_t *isbasic, double volumetol, int64_t *p_nupdate);
 
+/* Copying a handle (no reference counterpart): the complete logical state of src goes into the n handles dst[0..n) of
+ * the same m on the same device, so that many handles hold one factorization -- fresh or updated, a pending
+ * blu_hip_solve_for_update included -- and the batch entries above can continue from it, each member its own way.
+ * After a successful copy dst[k] is observably src: every blu_hip_get_param key, every blu_hip_get_stat key 0..124 (flop
+ * counters, totals, UPDATE_COST, NFACTORIZE, the timing keys, L_MEM / U_MEM / W_MEM) and blu_hip_set_skip_stats answer as
+ * on src, and every later call on dst[k] -- get_factors, the solves, solve_for_update, update, maxvolume, the batch entries,
+ * factorize -- returns the status, the pattern order and the bits the same call on src would have returned.  A pending
+ * update continues where src stands: blu_hip_update(dst[k], xtbl) right after the copy is valid when both solves had been
+ * made on src.  Afterwards src and every dst[k] are independent; src itself is unchanged (statistics, the caches it has
+ * built, its marker, a held blu_hip_solve_sparse_multi result).  Not part of the state, and the destination's own before
+ * and after: debug knobs, environment-read settings, the workspace pools (solve_dense_multi, solve_sparse_multi, the
+ * resident A of maxvolume) and the sparse workspace with its marker.  A blu_hip_solve_sparse_multi result dst[k] held is
+ * dropped (blu_hip_get_sparse_multi: BLU_ERROR_INVALID_CALL until the next multi call).  A source without a valid
+ * factorization (BLU_STAT_NUPDATE -1) makes every destination invalid in the same way; m == 0 copies the host state
+ * and launches nothing.
+ * Refused as a whole, every status[k] carrying the code and no handle touched: NULL src, dst or dst[k], n < 0
+ * (BLU_ERROR_ARGUMENT_MISSING); src among the destinations, a destination twice, on another device or with another m
+ * (BLU_ERROR_INVALID_ARGUMENT).  n == 0 returns BLU_OK.  Per member: BLU_ERROR_OUT_OF_MEMORY for a destination whose
+ * storage could not be grown -- it is left without a valid factorization (NUPDATE -1) but usable -- and the other members
+ * are copied regardless.  status may be NULL.  Returns the most negative member status, else the largest.
+ * Storage: what dst[k] has allocated is reused where it holds at least the capacity of src's array, and allocated anew
+ * with src's capacity otherwise; the capacity dst[k] then works with is src's, so it asks for storage exactly when src
+ * would.  A second copy into the same destination allocates nothing.  src keeps a staging block of under 1 KB per
+ * destination plus 4 KB.
+ * Cost, whatever n is: one upload (segment table, destination pointers, the destinations' descriptors), one launch of
+ * k_copy_fanout and one synchronize.  Only live extents are copied; the source is read once per group of up to 64
+ * destinations.  The row-wise L and the sorted U rows are not copied: dst[k] rebuilds them, with the same bits, at
+ * the first solve that needs them. */
+int blu_hip_copy_batch(blu_hip *src, blu_hip **dst, int n, int *status);
+/* blu_hip_new(m, src's b_nz, src's device) and blu_hip_copy_batch into it; NULL on any failure. */
+blu_hip *blu_hip_clone(blu_hip *src);
+/* The last blu_hip_copy_batch with this source: out[0] kernel launches, [1] synchronizes, [2] host-to-device copies,
+ * [3] device allocations made, [4] bytes of state read per destination, [5] bytes written to all destinations. */
+int blu_hip_dbg_copy_counts(const blu_hip *src, int64_t out[6]);
+
 /* factorize() ends with the statistics tail of src/factorize.rs:121-147 (condest(L), condest(U),
  * residual_test; getters BLU_STAT_CONDEST_* .. BLU_STAT_RESIDUAL_TEST).  It is a chain of 8 triangular
  * sweeps (~17 % of the factorize time at 100k); a caller that never reads those getters can switch

@@ -88,6 +88,8 @@ extern "C" {
         h: *mut BluHip, ncol: i64, a_p: *const u64, a_i: *const u64, a_x: *const f64, basis: *mut i64, isbasic: *mut i64, volumetol: f64,
         p_nupdate: *mut i64,
     ) -> c_int;
+    fn blu_hip_copy_batch(src: *mut BluHip, dst: *mut *mut BluHip, n: c_int, status: *mut c_int) -> c_int;
+    fn blu_hip_clone(src: *mut BluHip) -> *mut BluHip;
     fn blu_hip_last_error(h: *const BluHip) -> *const c_char;
 }
 
@@ -269,6 +271,19 @@ impl BLU {
             return None;
         }
         Some(BLU { lu: LU { h }, m, device, lhs: vec![0.0; m], ilhs: vec![0; m], nzlhs: 0, realloc_factor: 1.5 })
+    }
+
+    /// A new object with the complete logical state of this one (`blu_hip_clone`: factors, update state, a pending
+    /// `solve_for_update`, parameters and statistics), independent of it afterwards; `None` on any failure.  `lhs` / `ilhs` /
+    /// `nzlhs` are not carried over.  (Not `Clone`: the copy is device work and can fail.)
+    pub fn try_clone(&mut self) -> Option<BLU> {
+        self.push_realloc_factor();
+        let h = unsafe { blu_hip_clone(self.lu.h) };
+        if h.is_null() {
+            return None;
+        }
+        let m = self.m;
+        Some(BLU { lu: LU { h }, m, device: self.device, lhs: vec![0.0; m], ilhs: vec![0; m], nzlhs: 0, realloc_factor: self.realloc_factor })
     }
 
     // the library grows its device storage itself (the loops of blu.rs:105-115, 277-283, 324-330): it gets the factor
@@ -589,6 +604,31 @@ pub fn solve_sparse_batch(blus: &mut [&mut BLU], irhs: &[&[usize]], xrhs: &[&[f6
     for k in 0..n {
         if st[k] == 0 {
             blus[k].nzlhs = nz[k] as usize;
+        }
+    }
+    Ok(st.iter().map(|&s| status_of(s)).collect())
+}
+
+/// The complete logical state of `src` copied into every object of `dsts` (same `m`, same device) in one launch (batch
+/// extension, no reference counterpart): each is afterwards observably `src` and independent of it; its `lhs` / `ilhs` /
+/// `nzlhs` are cleared.  `Err` is a refusal of the whole call (another `m`, another device; the source among the
+/// destinations or a destination twice cannot be expressed here); otherwise one result per member.
+pub fn copy_batch(src: &mut BLU, dsts: &mut [&mut BLU]) -> Result<Vec<Result<(), Status>>, Status> {
+    let n = dsts.len();
+    src.push_realloc_factor();
+    let mut hs: Vec<*mut BluHip> = dsts.iter().map(|b| b.lu.h).collect();
+    let mut st = vec![0 as c_int; n];
+    let code = unsafe { blu_hip_copy_batch(src.lu.h, hs.as_mut_ptr(), n as c_int, st.as_mut_ptr()) };
+    if code == -3 || code == -4 {
+        return status_of(code).map(|_| Vec::new()); // (codes only a refusal returns)
+    }
+    for (k, b) in dsts.iter_mut().enumerate() {
+        if st[k] == 0 {
+            b.realloc_factor = src.realloc_factor;
+            for x in b.lhs.iter_mut() {
+                *x = 0.0;
+            }
+            b.nzlhs = 0;
         }
     }
     Ok(st.iter().map(|&s| status_of(s)).collect())

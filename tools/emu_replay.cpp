@@ -29,6 +29,10 @@
 //   OP_MAXVOLUME ncol a_p[ncol + 1] a_i[nnz] a_x[nnz] basis[m] isbasic[ncol] volumetol(double) with_nupdate status nupdate
 //               basis[m] isbasic[ncol]                      blu_hip_maxvolume with host arrays built here that end with their last
 //               entry (nnz = a_p[ncol], a_p[0] = 0); with_nupdate == 0 passes a NULL p_nupdate and nupdate is not compared
+//   OP_CLONE                                                the handle is replaced by its blu_hip_clone and the original freed: what
+//               the clone still shares with the original is a use-after-free report from here on
+//   OP_COPY_INTO b_nz                                       a new handle with that size hint receives blu_hip_copy_batch from the
+//               current one (status BLU_OK expected), the original is freed and the tape continues on the copy
 //   OP_END
 #include "../include/blu_hip.h"
 
@@ -47,12 +51,12 @@ extern "C" int blu_hip_dbg_set_sparse_multi_ws_bytes(blu_hip *h, int64_t bytes);
 extern "C" int blu_hip_dbg_set_maxvolume_chunk(blu_hip *h, int64_t n);
 
 enum { OP_END = 0, OP_NEW, OP_EXTRA, OP_PARAM, OP_FACT, OP_DENSE, OP_SPARSE, OP_FORUPD, OP_UPDATE, OP_STAT, OP_MULTI_WS, OP_DENSE_MULTI,
-       OP_SPARSE_MULTI_WS, OP_SPARSE_MULTI, OP_SPARSE_MULTI_GET, OP_MAXVOLUME, OP_MAXVOLUME_CHUNK };
+       OP_SPARSE_MULTI_WS, OP_SPARSE_MULTI, OP_SPARSE_MULTI_GET, OP_MAXVOLUME, OP_MAXVOLUME_CHUNK, OP_CLONE, OP_COPY_INTO };
 static const int64_t TAPE_MAGIC = 0x3145504154554c42LL; // "BLUTAPE1"
 static const char *const OP_NAME[] = {"end", "new", "dbg_set_upd_extra", "set_param", "factorize", "solve_dense", "solve_sparse",
                                       "solve_for_update", "update", "get_stat", "dbg_set_multi_ws_bytes", "solve_dense_multi",
                                       "dbg_set_sparse_multi_ws_bytes", "solve_sparse_multi", "get_sparse_multi", "maxvolume",
-                                      "dbg_set_maxvolume_chunk"};
+                                      "dbg_set_maxvolume_chunk", "clone", "copy_batch"};
 
 static std::vector<int64_t> tape;
 static size_t pos = 0;
@@ -137,7 +141,7 @@ int main(int argc, char **argv)
     int64_t m = 0;
     for (;;) {
         op = word();
-        if (op < OP_END || op > OP_MAXVOLUME_CHUNK) {
+        if (op < OP_END || op > OP_COPY_INTO) {
             fprintf(stderr, "emu_replay: unknown record %lld after call %ld\n", (long long)op, ncall);
             return 2;
         }
@@ -302,6 +306,23 @@ int main(int argc, char **argv)
             if (with_nupdate) same_int("nupdate", nupdate, want_nupdate);
             same_words("basis", basis.data(), take(M), M, false);
             same_words("isbasic", isbasic.data(), take(ncol), ncol, false);
+            break;
+        }
+        case OP_CLONE: {
+            blu_hip *c = blu_hip_clone(h);
+            same_int("clone", c != nullptr, 1);
+            blu_hip_free(h);
+            h = c;
+            break;
+        }
+        case OP_COPY_INTO: {
+            blu_hip *c = blu_hip_new(m, word(), 0);
+            same_int("handle", c != nullptr, 1);
+            int status = -99;
+            same_int("return value", blu_hip_copy_batch(h, &c, 1, &status), BLU_OK);
+            same_int("status", status, BLU_OK);
+            blu_hip_free(h);
+            h = c;
             break;
         }
         case OP_STAT: {
