@@ -92,11 +92,12 @@ struct Scalars {
     long long nfast[4];        // k_pivot_loop_wave: pivots taken by its flattened paths (small, singleton col), searches handed over by the previous pivot
     long long nrun[4];         // k_pivot_loop: singleton-column pivots whose search was found early / whose set-up was done early too (barrier merged);
                                // small pivots entered through a merged barrier / singleton-column pivots entered so after a small pivot
+    long long nsplit[2];       // k_pivot_loop: early set-ups of small pivots completed on two waves / hand-overs between the two waves abandoned at the bound of a wait
     double min_pivot, max_pivot;
     double onenorm, infnorm;
     double norm_l, norm_u, normest_l_inv, normest_u_inv, condest_l, condest_u, residual_test;
     long long prof[48];    // diagnostic build only (-DBLU_PROFILE): shader-clock ticks per phase of the pivot loop
-    long long prof2[14];   // the same, k_pivot_loop only: singleton-column pivots (search + set-up, finalize step per wave); small pivots by how they were entered
+    long long prof2[20];   // the same, k_pivot_loop only: singleton-column pivots (search + set-up, finalize step per wave); small pivots by how they were entered
 };
 
 // Scalar members of the descriptor: dimensions, parameters (public fields of struct LU,

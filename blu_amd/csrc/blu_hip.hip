@@ -602,8 +602,10 @@ extern "C" double blu_hip_get_stat(const blu_hip *h, int key)
     case 121: case 122: return (double)s.nrun[key - 121]; // k_pivot_loop, singleton-column pivots: search found early / set-up done early as well (two barriers instead of three)
     case 123: return (double)s.nrun[2]; // k_pivot_loop, barrier merged as for 122: small pivots set up during the finalize step of their predecessor
     case 125: return (double)s.nrun[3]; // ... singleton-column pivots set up during the finalize step of a small pivot (124 is BLU_STAT_UPDATE_COST)
+    case 127: case 128: return (double)s.nsplit[key - 127]; // k_pivot_loop: small pivots of 123 whose set-up was made on two waves / hand-overs of such set-ups abandoned at the bound of a wait (a defect: 0)
     case 126: return (double)h->chain_defects; // statistics chains of this handle abandoned by a bounded wait and recomputed by k_stats (k_chain.h)
     case 131: case 132: case 133: case 134: case 135: case 136: case 137: case 138: case 139: case 140: case 141: case 142: case 143: case 144:
+    case 145: case 146: case 147: case 148: case 149: case 150:
         return (double)s.prof2[key - 131]; // diagnostic build only
     case 57: return (double)s.err_line;
     case 58: return (double)s.status;

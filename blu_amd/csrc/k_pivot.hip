@@ -47,7 +47,7 @@ __shared__ int g_pivot_err_line; // source line of a bounded loop that overran (
 // Diagnostic build (-DBLU_PROFILE, `make prof`): thread 0 stamps the shader clock at phase boundaries
 // of the pivot loop.  The product build contains no stamps.
 #ifdef BLU_PROFILE
-__shared__ long long g_pstamp[56];
+__shared__ long long g_pstamp[64];
 #define PROF_STAMP(k)                                                      \
     do {                                                                   \
         if (threadIdx.x == 0) g_pstamp[k] = (long long)__builtin_amdgcn_s_memtime(); \
@@ -84,7 +84,7 @@ struct alignas(16) Sm {
     };
 #ifdef BLU_PROFILE
     long long prof[48];
-    long long prof2[14];
+    long long prof2[20];
 #else
     long long prof[1];
 #endif
@@ -102,6 +102,12 @@ struct alignas(16) Sm {
     int nx_whole;        // 1: set up after a whole speculative search (small_setup_next), 0: after a column singleton found early
     int mg; // 1: the barrier that ended the finalize step was also the barrier after the next pivot's set-up
     long long nrun[4];
+    // hand-over between the two waves of an early set-up after a whole speculative search (small_setup_next on the speculating
+    // wave, small_setup_help on wave 0).  Both words are 0 from the barrier after the line updates on.
+    volatile int hs_go;   // 0 pending, 1 key published (spKey), 2 nothing to set up
+    volatile int hs_done; // 0 pending, 1 column side of *nxt written and hs_gr valid, 2 abandoned (a wait ran into its bound)
+    long long hs_gr;      // the helper's room sum: row-arena estimate of the rows of the next pivot column
+    long long nsplit[2];  // set-ups of small pivots completed on two waves / hand-overs that ran into the bound of a wait
 #endif
     int rank, rankdef, min_colnz, min_rownz;
     int cused, rused, lused, uused;
@@ -1267,10 +1273,14 @@ __device__ __forceinline__ void pivot_loop_body(DevLU *Ds, int stop_at, Sm *sm, 
         for (int k = 0; k < 6; k++) sm->kinds[k] = 0;
         sm->mg = 0;
         sm->nrun[0] = sm->nrun[1] = sm->nrun[2] = sm->nrun[3] = 0;
+        sm->nsplit[0] = sm->nsplit[1] = 0;
+        sm->hs_go = 0;
+        sm->hs_done = 0;
+        sm->hs_gr = 0;
 #ifdef BLU_PROFILE
         for (int k = 0; k < 48; k++) sm->prof[k] = 0;
-        for (int k = 0; k < 14; k++) sm->prof2[k] = 0;
-        for (int k = 0; k < 56; k++) g_pstamp[k] = 0;
+        for (int k = 0; k < 20; k++) sm->prof2[k] = 0;
+        for (int k = 0; k < 64; k++) g_pstamp[k] = 0;
 #endif
     }
     for (int k = tid; k < (int)blockDim.x; k += blockDim.x) sm->swork[k] = 0.0; // num_waves() x 64
@@ -1346,6 +1356,13 @@ __device__ __forceinline__ void pivot_loop_body(DevLU *Ds, int stop_at, Sm *sm, 
                     PROF_ADD(46, 45, 3);  // spec_finish done
                     PROF_ADD(47, 46, 3);  // set-up done (or given up)
                     sm->prof2[7] += 1;
+                    // the stages of that wave's path, each relative to the same barrier
+                    PROF_ADD2(14, 52, 3); // merged
+                    PROF_ADD2(15, 53, 3); // candidate entries arrived
+                    PROF_ADD2(16, 54, 3); // their rows' records arrived
+                    PROF_ADD2(17, 55, 3); // set-up's preamble done: key decoded, shape and room pre-checks
+                    PROF_ADD2(18, 56, 3); // pivot row arrived
+                    PROF_ADD2(19, 57, 3); // records of its columns arrived
                 }
             }
             if (kk == 2) {
@@ -1565,9 +1582,10 @@ __device__ __forceinline__ void pivot_loop_body(DevLU *Ds, int stop_at, Sm *sm, 
         S->d3_hits += sm->d3;
         for (int k = 0; k < 6; k++) S->npivot_kind[k] += sm->kinds[k];
         for (int k = 0; k < 4; k++) S->nrun[k] += sm->nrun[k];
+        for (int k = 0; k < 2; k++) S->nsplit[k] += sm->nsplit[k];
 #ifdef BLU_PROFILE
         for (int k = 0; k < 48; k++) S->prof[k] += sm->prof[k];
-        for (int k = 0; k < 14; k++) S->prof2[k] += sm->prof2[k];
+        for (int k = 0; k < 20; k++) S->prof2[k] += sm->prof2[k];
 #endif
         if (sm->exit_code == ST_ERROR && g_pivot_err_line) set_error(S, ST_ERROR, g_pivot_err_line);
         if (S->status == ST_RUNNING) S->status = sm->exit_code;

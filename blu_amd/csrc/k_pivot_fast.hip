@@ -1547,6 +1547,9 @@ __device__ __forceinline__ void early_search(const DevGP &D, Sm *sm, Mc *mc, con
             const double x = fabs(val);
             if (x == 0.0 || x < tol) return;
             nsr = left < K ? left : K;
+            // (Tried on the route without a round trip, fs >= 0: the load of the pivot row issued here from registers, ahead of the
+            // staging stores and the fence, and pc / pr / prb / nzr handed to scol_setup_next in registers: 693.8 -> 694.6 ms per
+            // step, third library in the rotation of profiles/setup_split_ab.txt.  Not kept.)
             if (lane == 0) {
                 fa->ncand = 1;
                 fa->cJ[0] = j;
@@ -1684,11 +1687,20 @@ __device__ __forceinline__ bool spec_cond(const Sm *sm, const Fast *cs, const in
 // (ewValid = 2).  (Staging before the barrier and only the costs here was measured too: the barrier comes later
 // by more than this step gets shorter, 699 -> 707 ms.)
 // cs = working set of the pivot being finished: new counts, begins and maxima of the columns it updated
-__device__ __forceinline__ void spec_finish(const DevGP &D, Sm *sm, const Fast *cs, int n)
+// The winner stays in registers (win): its key, the candidate it belongs to, and row, length and begin of the pivot row, which
+// the lane that staged the winning entry still holds.  small_setup_next publishes the result (spKey, ewValid = 2) -- after it
+// has issued the load of the pivot row, so that nothing the next round trip needs is read back from LDS first.
+struct SpecWin {
+    long long key; // cost * 256 + flat position; < 0: no result (more entries than the staging arrays hold, or none eligible)
+    int csel, coff; // candidate of the winning entry, flat position of its first entry
+    int pr, nzr, prb;
+};
+__device__ __forceinline__ void spec_finish(const DevGP &D, Sm *sm, const Fast *cs, int n, SpecWin &win)
 {
     const int lane = lane_id();
     Fast *fa = &sm->fa;
     const int ncand = fa->ncand;
+    win.key = -1;
     // ---- merge.  The next search walks, count by count, the unmoved columns of a list in their old order and then
     // the columns this pivot appended to it, in pivot-row order.  The walk has the first K unmoved ones (counts
     // ascending, the last one's = spLastNz); an updated column comes before the K-th candidate exactly if its new
@@ -1750,13 +1762,14 @@ __device__ __forceinline__ void spec_finish(const DevGP &D, Sm *sm, const Fast *
             SPEC_STAT(4);
         }
     }
+    PROF_STAMP_L0(52); // merged
     const int total = fa->cOff[ncand];
     if (total > STGMAX) return;
     const int off1 = ncand > 1 ? fa->cOff[1] : 0x7fffffff, off2 = ncand > 2 ? fa->cOff[2] : 0x7fffffff,
               off3 = ncand > 3 ? fa->cOff[3] : 0x7fffffff;
     const long long BIG = 0x7fffffffffffffffLL;
     long long mcb = BIG;
-    int fb = 0x7fffffff;
+    int fb = 0x7fffffff, bI = 0, bL = 0, bB = 0; // (row, its length and begin of this lane's best entry)
     for (int base = 0; base < total; base += 64) {
         const int f = base + lane;
         if (f < total) {
@@ -1764,7 +1777,15 @@ __device__ __forceinline__ void spec_finish(const DevGP &D, Sm *sm, const Fast *
             const int pos = fa->cB[c] + (f - fa->cOff[c]);
             const int idx = D.cidx[pos];
             const double val = D.cval[pos];
+            if (base == 0) {
+                PROF_WAIT();
+                PROF_STAMP_L0(53); // candidate entries arrived
+            }
             const int rb = D.rbeg[idx], rl = D.rlen[idx], rc = D.rcap[idx];
+            if (base == 0) {
+                PROF_WAIT();
+                PROF_STAMP_L0(54); // their rows' records arrived
+            }
             fa->sI[f] = idx;
             fa->sV[f] = val;
             fa->sB[f] = rb;
@@ -1777,6 +1798,9 @@ __device__ __forceinline__ void spec_finish(const DevGP &D, Sm *sm, const Fast *
                 if (cost < mcb) {
                     mcb = cost;
                     fb = f;
+                    bI = idx;
+                    bL = rl;
+                    bB = rb;
                 }
             }
         }
@@ -1787,20 +1811,51 @@ __device__ __forceinline__ void spec_finish(const DevGP &D, Sm *sm, const Fast *
     const long long key = wave_min_ll(mcb != BIG ? mcb * 256LL + (long long)fb : BIG);
     if (key == BIG) return;
     SPEC_STAT(3);
-    if (lane == 0) {
-        fa->spKey = key;
-        fa->ewNsr = ncand;
-        fa->ewValid = 2;
-    }
-    wave_mem_sync();
+    const int fsel = (int)(key & 255LL);
+    const int wl = fsel & 63; // (flat position f was staged by lane f & 63)
+    win.key = key;
+    win.csel = (fsel >= off1) + (fsel >= off2) + (fsel >= off3);
+    win.coff = win.csel == 0 ? 0 : (win.csel == 1 ? off1 : (win.csel == 2 ? off2 : off3));
+    win.pr = wave_bcast_i(bI, wl);
+    win.nzr = wave_bcast_i(bL, wl);
+    win.prb = wave_bcast_i(bB, wl);
     PROF_STAMP_L0(44);
+}
+
+// ------------------------------------------------------------------------------------------------
+// Hand-over words of the two-wave early set-up (Sm::hs_go, hs_done).  Other waves poll them, so they are volatile, and they
+// are read and written with the LDS address space spelled out: a volatile access through a generic pointer stays a FLAT
+// instruction, which waits for the wave's outstanding global loads as well (ch_flag / ch_set in k_chain.h, DESIGN.md "A ring
+// of chain waves").  Writer: data, release fence at workgroup scope, flag.  Reader: flag, acquire fence, data.
+// Every wait is bounded: HS_SPIN polls one after the other, then polls with a sleep between them, HS_BOUND in all (of the
+// order of 0.1 s against the few microseconds of a finalize step); hs_wait returns 0 when it ran out.
+// ------------------------------------------------------------------------------------------------
+#ifdef BLU_EMU_BUILD
+#define HS_LDS(T) T *
+#else
+#define HS_LDS(T) __attribute__((address_space(3))) T *
+#endif
+#define HS_SPIN 64
+#define HS_BOUND (1 << 20)
+__device__ __forceinline__ int hs_get(const volatile int *p) { return *(HS_LDS(const volatile int))p; }
+__device__ __forceinline__ void hs_put(volatile int *p, int v) { *(HS_LDS(volatile int))p = v; }
+__device__ __forceinline__ int hs_wait(const volatile int *p)
+{
+    int v = hs_get(p);
+    for (int it = 0; v == 0 && it < HS_BOUND; it++) {
+        if (it >= HS_SPIN) __builtin_amdgcn_s_sleep(1);
+        v = hs_get(p);
+    }
+    return v;
 }
 
 // ------------------------------------------------------------------------------------------------
 // kind 1, whole workgroup
 // ------------------------------------------------------------------------------------------------
+struct SpecWin;
 __device__ __forceinline__ bool scol_setup_next(const DevGP &D, Sm *sm, Mc *mc, Fast *nxt, int rl_cur);
-__device__ __forceinline__ bool small_setup_next(const DevGP &D, Sm *sm, Mc *mc, Fast *nxt, int cnz1_cur, int rnz1_cur);
+__device__ __forceinline__ bool small_setup_next(const DevGP &D, Sm *sm, Mc *mc, Fast *nxt, int cnz1_cur, int rnz1_cur, const SpecWin &win);
+__device__ __forceinline__ void small_setup_help(const DevGP &D, Sm *sm, Fast *nxt);
 // fa = the working set of this pivot: sm->fa as mk_pick laid it out, or the set that small_setup_next / scol_setup_next laid
 // out during the finalize step of the previous pivot (sm->fa and sm->fb alternate while barriers are merged).  The staging
 // fields (c*, s*, ew*, sp*, kg) are those of sm->fa always.
@@ -1899,6 +1954,12 @@ __device__ __forceinline__ void fast_small(const DevGP &D, Sm *sm, Mc *mc, Fast 
         PROF_STAMP_L0(38);
     }
 #endif
+    // the hand-over words of the two-wave set-up are 0 from the barrier below on: cleared by the wave with the fewest line
+    // updates, once it is done with them (their last readers left them before the barrier that ended the previous finalize step)
+    if (early && w == nwt - 1 && lane == 0) {
+        hs_put(&sm->hs_go, 0);
+        hs_put(&sm->hs_done, 0);
+    }
     PROF_STAMP(5);
     __syncthreads();
     PROF_STAMP(3);
@@ -1912,7 +1973,8 @@ __device__ __forceinline__ void fast_small(const DevGP &D, Sm *sm, Mc *mc, Fast 
     // The wave that found the next pivot goes on to set it up on the other working set (small_setup_next after a whole
     // speculative search, scol_setup_next after a column singleton found by wave 0) and says so in sm->mg, which every
     // wave reads right after the barrier below.  Exactly one wave writes that word: the speculating wave if the
-    // speculation holds (both waves evaluate spec_cond on the same LDS words), wave 0 otherwise.
+    // speculation holds (both waves evaluate spec_cond on the same LDS words), wave 0 otherwise.  When it holds, wave 0 -- on
+    // another SIMD, and without a job of its own then -- takes the column side of that set-up (small_setup_help).
     const bool spec = early && (w == 0 || w == nw - 1) && spec_cond(sm, fa, fa->tNew + 1, rnz1);
     Fast *other = fa == &sm->fa ? &sm->fb : &sm->fa;
     if (w == 0 && !spec) {
@@ -1923,10 +1985,11 @@ __device__ __forceinline__ void fast_small(const DevGP &D, Sm *sm, Mc *mc, Fast 
         }
         if (lane == 0) sm->mg = merged ? 1 : 0;
     }
+    if (w == 0 && spec) small_setup_help(D, sm, other);
     if (w == nw - 1 && spec) {
-        spec_finish(D, sm, fa, rnz1);
-        PROF_STAMP_L0(45);
-        const bool merged = small_setup_next(D, sm, mc, other, cnz1, rnz1);
+        SpecWin win;
+        spec_finish(D, sm, fa, rnz1, win);
+        const bool merged = small_setup_next(D, sm, mc, other, cnz1, rnz1, win); // (stamp 45: result published)
         if (lane == 0) sm->mg = merged ? 1 : 0;
         PROF_STAMP_L0(46);
     }
@@ -2043,6 +2106,13 @@ __device__ __forceinline__ bool scol_setup_next(const DevGP &D, Sm *sm, Mc *mc, 
 // U and list waves are still reading the current one, and the barrier that ends the finalize step is then also the
 // barrier after the set-up (sm->mg), as inside a run of singleton-column pivots.  Only the straight-line shape of mk_pick
 // is taken (row and column of at most 64 entries, kind 1 or 2).
+// The set-up is split over two waves.  This wave has the winner in registers (SpecWin): it runs the pre-checks, issues the load
+// of the pivot row, only then publishes the key and the go word (Sm::hs_go), and goes on with the row side: hCol, the records
+// of the row's columns, tJ / tB / tL / tC, the column-arena sum.  Wave 0, idle in a finalize step whose speculation holds and
+// on another SIMD, takes the column side (small_setup_help): pivot column and the records of its rows into *nxt, hRow, the
+// row-arena sum -- LDS only, nothing of it needs the two round trips.  This wave waits for the helper's done word before the
+// arena test and the dispatch words; both waits are bounded, a wait that runs out sends the pivot through the ordinary head
+// (statistic 128; 127 counts the set-ups of small pivots completed on two waves and equals 123).
 //   * Final at this moment, and read from global memory or from what spec_finish staged after the barrier: entries and
 //     (begin, len, cap) of every row and column, colmax, cused / rused.  The barrier after the line updates made them
 //     final; fast_fixrow runs only after a cancellation, and then nothing was speculated (spec_cond).  The finalize step
@@ -2061,23 +2131,23 @@ __device__ __forceinline__ bool scol_setup_next(const DevGP &D, Sm *sm, Mc *mc, 
 // Returns true when *nxt and the sm->nx_* words describe the next pivot.  `make ewcheck` compares each such set-up with
 // the ordinary search + mk_pick (small_setup_check).
 // ------------------------------------------------------------------------------------------------
-__device__ __forceinline__ bool small_setup_next(const DevGP &D, Sm *sm, Mc *mc, Fast *nxt, int cnz1_cur, int rnz1_cur)
+__device__ __forceinline__ bool small_setup_next(const DevGP &D, Sm *sm, Mc *mc, Fast *nxt, int cnz1_cur, int rnz1_cur, const SpecWin &win)
 {
     const int lane = lane_id();
     Fast *st = &sm->fa; // where spec_finish stages
-    if (st->ewValid != 2) return false;
-    if (g_pivot_err || mc->dirty) return false;
-    const int nrd = sm->rank + 1 + sm->rankdef; // what the loop head would see
-    if (nrd >= D.m || (sm->stop_at >= 0 && nrd >= sm->stop_at)) return false;
+    if (win.key < 0) { // spec_finish gave up: nothing published (ewValid stays 0), the helper leaves, the ordinary head searches
+        if (lane == 0) hs_put(&sm->hs_go, 2);
+        return false;
+    }
+    // the pivot from the winner in registers; of the candidate only what one round of LDS reads gives
     const int ncand = st->ncand;
-    const int off1 = ncand > 1 ? st->cOff[1] : 0x7fffffff, off2 = ncand > 2 ? st->cOff[2] : 0x7fffffff,
-              off3 = ncand > 3 ? st->cOff[3] : 0x7fffffff;
-    const int fsel = (int)(st->spKey & 255LL);
-    const int csel = (fsel >= off1) + (fsel >= off2) + (fsel >= off3);
-    const int coff = st->cOff[csel];
-    const int pc = st->cJ[csel], pr = st->sI[fsel];
-    const int nzc = st->cL[csel], pcb = st->cB[csel], where = fsel - coff;
-    const int nzr = st->sL[fsel], prb = st->sB[fsel];
+    const int csel = win.csel, coff = win.coff;
+    const int pc = st->cJ[csel], nzc = st->cL[csel], pcb = st->cB[csel], minc = st->cNz[0];
+    const int pr = win.pr, nzr = win.nzr, prb = win.prb;
+    const int where = (int)(win.key & 255LL) - coff;
+    bool go = !(g_pivot_err || mc->dirty);
+    const int nrd = sm->rank + 1 + sm->rankdef; // what the loop head would see
+    if (nrd >= D.m || (sm->stop_at >= 0 && nrd >= sm->stop_at)) go = false;
     // (the shape test of mk_pick's straight-line form: a row of exactly 64 is in, for either kind -- fast_scol takes such a row
     // from the ordinary head as well, with the unsplit form of its list update and nothing set up early behind it;
     // scol_setup_next keeps to rows shorter than 64, the split form, which is all a run needs)
@@ -2086,27 +2156,26 @@ __device__ __forceinline__ bool small_setup_next(const DevGP &D, Sm *sm, Mc *mc,
         if (nzc == 1) kind = 2;
         else if (nzc >= 3 && nzc <= 64) kind = 1;
     }
-    if (kind == 0) return false;
-    if ((long long)sm->lused + cnz1_cur + (nzc - 1) > (long long)D.lcap || (long long)sm->uused + rnz1_cur + (nzr - 1) > (long long)D.ucap) return false;
-    // ---- from here on as the straight-line form of mk_pick, on *nxt
-    const int jq0 = lane < nzr ? D.ridx[prb + lane] : -1;
-    if (kind == 1) {
-        for (int s = lane; s < HROW; s += 64) nxt->hRow[s] = ~0ull;
+    if (kind == 0) go = false;
+    if ((long long)sm->lused + cnz1_cur + (nzc - 1) > (long long)D.lcap || (long long)sm->uused + rnz1_cur + (nzr - 1) > (long long)D.ucap) go = false;
+    PROF_STAMP_L0(55); // preamble: key decoded, shape and room pre-checks
+    // ---- the load of the pivot row first, then the result for the next search and the word the helper waits for: 1 = the key
+    // is published and the set-up is under way, 2 = on any way out.  ewValid reads 2 on every way out from here: the ordinary
+    // head picks the staged search up.
+    const int jq0 = go && lane < nzr ? D.ridx[prb + lane] : -1;
+    if (lane == 0) {
+        st->spKey = win.key;
+        st->ewNsr = ncand;
+        st->ewValid = 2;
     }
+    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup"); // (the staged entries of every lane, and the three words above)
+    if (lane == 0) hs_put(&sm->hs_go, go ? 1 : 2);
+    PROF_STAMP_L0(45);
+    if (!go) return false;
+    // ---- the row side, as the straight-line form of mk_pick, on *nxt
     for (int s = lane; s < HCOL; s += 64) nxt->hCol[s] = ~0ull;
-    int hr_idx0 = 0, hr_slot0 = 0, hr_len0 = 0;
-    if (lane < nzc) {
-        const int slot = (lane == where) ? 0 : (lane == 0 ? where : lane);
-        const int idx = st->sI[coff + lane], rlv = st->sL[coff + lane];
-        nxt->pcI[slot] = idx;
-        nxt->pcV[slot] = st->sV[coff + lane];
-        nxt->prB[slot] = st->sB[coff + lane];
-        nxt->prL[slot] = rlv;
-        nxt->prC[slot] = st->sC[coff + lane];
-        hr_slot0 = slot;
-        hr_idx0 = idx;
-        hr_len0 = rlv;
-    }
+    PROF_WAIT();
+    PROF_STAMP_L0(56); // pivot row arrived
     const unsigned long long hb = __ballot(jq0 == pc);
     if (!hb) return false; // (the ordinary set-up raises the error)
     const int wpos = __ffsll((long long)hb) - 1;
@@ -2116,12 +2185,9 @@ __device__ __forceinline__ bool small_setup_next(const DevGP &D, Sm *sm, Mc *mc,
         tl = D.clen[jq0];
         tc = D.ccap[jq0];
     }
-    int gc = 0, gr = 0;
-    if (kind == 1 && hr_slot0 >= 1) {
-        hrow_insert(nxt, hr_idx0, hr_slot0);
-        const int n = hr_len0 + nzr - 1;
-        gr = n + stretch_of(D.stretch, n) + D.pad;
-    }
+    PROF_WAIT();
+    PROF_STAMP_L0(57); // records of the pivot row's columns arrived
+    int gc = 0;
     if (lane < nzr) {
         const int slot = kind == 1 ? ((lane == wpos) ? 0 : (lane == 0 ? wpos : lane)) : lane;
         nxt->tJ[slot] = jq0;
@@ -2134,9 +2200,17 @@ __device__ __forceinline__ bool small_setup_next(const DevGP &D, Sm *sm, Mc *mc,
             gc = n + stretch_of(D.stretch, n) + D.pad;
         }
     }
+    long long gcs = 0;
+    if (kind == 1) gcs = wave_sum_ll((long long)gc);
+    // ---- the column side is the helper's: wait for it, then the arena test with both sums (each below 2^31, as in mk_pick)
+    const int dn = hs_wait(&sm->hs_done);
+    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "workgroup");
+    if (dn != 1) { // the helper gave up (it has counted that), or this wait ran out: the ordinary head sets the pivot up
+        if (dn == 0 && lane == 0) atomicAdd((unsigned long long *)&sm->nsplit[1], 1ull);
+        return false;
+    }
     if (kind == 1) {
-        const long long both = wave_sum_ll(((long long)gc << 32) | (long long)(unsigned)gr);
-        if ((long long)sm->cused + (both >> 32) > (long long)D.carena_cap || (long long)sm->rused + (both & 0xffffffffLL) > (long long)D.rarena_cap)
+        if ((long long)sm->cused + gcs > (long long)D.carena_cap || (long long)sm->rused + sm->hs_gr > (long long)D.rarena_cap)
             return false; // mk_pick hands such a pivot to the general path
     }
     if (lane == 0) {
@@ -2152,12 +2226,62 @@ __device__ __forceinline__ bool small_setup_next(const DevGP &D, Sm *sm, Mc *mc,
         sm->nx_kind = kind;
         sm->nx_prb = prb;
         sm->nx_pcb = pcb;
-        sm->nx_nsr = st->ewNsr;
-        sm->nx_minc = st->cNz[0];
+        sm->nx_nsr = ncand;
+        sm->nx_minc = minc;
         sm->nx_whole = 1;
         st->ewValid = 0;
+        if (kind == 1) sm->nsplit[0]++;
     }
     return true;
+}
+
+// The column side of that set-up, on wave 0: the pivot column with the (begin, len, cap) of its rows from the staging arrays
+// into *nxt, the row hash, the row-arena sum.  LDS only.  It starts when the speculating wave has published the key -- the
+// moment that wave's load of the pivot row goes out -- and is done long before the two round trips of the row side are.
+// A singleton column (kind 2) has no row hash: the five words of slot 0 are all there is.  A wait that runs out ends the
+// hand-over (hs_done = 2, statistic 128) and the pivot goes through the ordinary head; every way out reaches the barrier that
+// ends the finalize step, and nothing is written to *nxt after it.
+__device__ __forceinline__ void small_setup_help(const DevGP &D, Sm *sm, Fast *nxt)
+{
+    const int lane = lane_id();
+    Fast *st = &sm->fa;
+    for (int s = lane; s < HROW; s += 64) nxt->hRow[s] = ~0ull; // (needs nothing from the search; unused by a kind-2 pivot)
+    const int go = hs_wait(&sm->hs_go);
+    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "workgroup");
+    if (go != 1) {
+        if (go == 0 && lane == 0) {
+            hs_put(&sm->hs_done, 2);
+            atomicAdd((unsigned long long *)&sm->nsplit[1], 1ull);
+        }
+        return;
+    }
+    const int ncand = st->ncand;
+    const int off1 = ncand > 1 ? st->cOff[1] : 0x7fffffff, off2 = ncand > 2 ? st->cOff[2] : 0x7fffffff,
+              off3 = ncand > 3 ? st->cOff[3] : 0x7fffffff;
+    const int fsel = (int)(st->spKey & 255LL);
+    const int csel = (fsel >= off1) + (fsel >= off2) + (fsel >= off3);
+    const int coff = st->cOff[csel];
+    const int nzc = st->cL[csel], where = fsel - coff; // (1, or 3..64: the speculating wave has tested the shape)
+    const int nzr = st->sL[fsel];
+    int gr = 0;
+    if (lane < nzc) {
+        const int slot = (lane == where) ? 0 : (lane == 0 ? where : lane);
+        const int idx = st->sI[coff + lane], rlv = st->sL[coff + lane];
+        nxt->pcI[slot] = idx;
+        nxt->pcV[slot] = st->sV[coff + lane];
+        nxt->prB[slot] = st->sB[coff + lane];
+        nxt->prL[slot] = rlv;
+        nxt->prC[slot] = st->sC[coff + lane];
+        if (nzc >= 3 && slot >= 1) {
+            hrow_insert(nxt, idx, slot);
+            const int n = rlv + nzr - 1;
+            gr = n + stretch_of(D.stretch, n) + D.pad;
+        }
+    }
+    const long long grs = wave_sum_ll((long long)gr);
+    if (lane == 0) sm->hs_gr = grs;
+    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup");
+    if (lane == 0) hs_put(&sm->hs_done, 1);
 }
 
 #ifdef BLU_EWCHECK

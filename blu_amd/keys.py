@@ -74,3 +74,7 @@ STAT_NSYMPERM_TOTAL = 48
 STAT_NFORREST_TOTAL = 49
 STAT_DEV_NUNSYMPERM_TOTAL = 59
 STAT_UPDATE_COST = 124
+# k_pivot_loop, early set-up of a small pivot split over two waves (k_pivot_fast.hip: small_setup_next + small_setup_help).
+# Device-only diagnostics like 121..126, which have no names here: not STAT_*, the names of what the oracle answers as well.
+DEVSTAT_SETUP_TWO_WAVES = 127   # set-ups of small pivots completed on two waves (equals statistic 123)
+DEVSTAT_SETUP_ABANDONED = 128   # hand-overs between the two waves that ran into the bound of a wait (a defect: 0)

@@ -57,6 +57,14 @@ ns = max(1, q[7])
 st = lambda k: 0 if h.stat(k) != h.stat(k) else h.stat(k)  # (a library from before these statistics answers NaN)
 print("small merge : %d of %d small pivots entered through the merged barrier (stat 123), %d singleton-column pivots after a small one (stat 125); speculating wave in %d finalize steps: spec_finish done @%.2f us, early set-up done @%.2f us (U row @%.2f, L column @%.2f us: the helpers wait from there)"
       % (st(123), p[4], st(125), q[7], p[46] * f / ns, p[47] * f / ns, cyc(22) * f, cyc(23) * f))
+# the path of the speculating wave through those finalize steps, stage by stage (keys 145..150, then 106 and 107): cycles from
+# the end of one stage to the end of the next; the first one counts from the barrier after the line updates
+r = [st(145 + k) for k in range(6)] + [p[46], p[47]]
+stages = ["merge", "candidate entries", "row records", "preamble (key decoded, pre-checks)", "pivot row", "column records",
+          "result published", "rest of the set-up (hashes, sums, dispatch words)"]
+ends, stages = zip(*sorted(zip([x / ns for x in r], stages)))  # (the result is published before or after the preamble, by build)
+print("setup tail  : cycles per stage on the speculating wave: " + " | ".join("%s %.0f" % (nm, ends[k] - (ends[k - 1] if k else 0)) for k, nm in enumerate(stages))
+      + " || ends @%.0f cycles = %.2f us" % (ends[-1], ends[-1] * f))
 # the same pivots by how they were entered (keys 139..144): whole time from the barrier, or the loop head, a small pivot starts at
 # to the barrier that ends it -- search + set-up included where it had one of its own -- and its finalize step, which holds the
 # early set-up of the NEXT pivot where one was made
