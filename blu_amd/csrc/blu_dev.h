@@ -283,6 +283,37 @@ template <class T> struct ColdArr {
     __device__ __forceinline__ __attribute__((address_space(1))) T &operator[](size_t i) const { return get()[i]; }
     __device__ __forceinline__ GPTR(T) operator+(int i) const { return get() + i; }
 };
+// The same for the parameters and capacities: held by value they are ~20 more scalar registers live across the whole pivot
+// loop (the four tolerances alone are eight), spilled and reloaded lane by lane wherever one is used.  A ColdVal reads its
+// word from the descriptor where it is used: one load through the scalar cache (constant address space: the descriptor is
+// not written while a kernel runs), no vector instruction.  m, search_rows, no_fast and skip_stats stay values.
+// (Not built: copies of droptol / abstol in LDS for the lone-wave tails)
+#define DEVLU_SCALARS_HELD(X) X(int, m) X(int, search_rows) X(int, no_fast) X(int, skip_stats)
+#define DEVLU_SCALARS_COLD(X)                                                                          \
+    X(int, nzbias) X(int, maxsearch) X(int, pad)                                                       \
+    X(double, droptol) X(double, abstol) X(double, reltol) X(double, stretch)                          \
+    X(long long, b_i_len) X(int, nzcap) X(int, carena_cap) X(int, rarena_cap) X(int, lcap) X(int, ucap)
+#define X(T, n) +1
+static_assert((0 DEVLU_SCALARS(X)) == (0 DEVLU_SCALARS_HELD(X) DEVLU_SCALARS_COLD(X)), "DEVLU_SCALARS_HELD + _COLD must list every member of DEVLU_SCALARS");
+#undef X
+template <class T> struct ColdVal {
+    const __attribute__((address_space(4))) T *slot; // where the value sits inside the descriptor
+    __device__ __forceinline__ operator T() const { return *slot; }
+};
+// And of the HOT arrays, the six that a pivot touches once or twice, in its finalize step, are fetched like the COLD ones;
+// the line records, the arenas and the factors stay in registers.  (The slab residents as 32-bit offsets from one base, and
+// array indices zero-extended through an accessor, were not built.)
+#define DEVLU_ARRAYS_PIVOT_FETCHED(X) X(int, pinv) X(int, qinv) X(int, prow) X(int, pcol) X(int, lbeg) X(int, ubeg)
+#define DEVLU_ARRAYS_PIVOT_HELD(X)                                                                     \
+    X(LineRec, crec) X(LineRec, rrec) X(HeadRec, chead) X(HeadRec, rhead)                              \
+    X(int, cidx) X(double, cval) X(int, ridx)                                                          \
+    X(int, lidx) X(int, uidx) X(double, lval) X(double, uval)
+#define X(T, n) +1
+static_assert((0 DEVLU_ARRAYS_HOT(X)) == (0 DEVLU_ARRAYS_PIVOT_HELD(X) DEVLU_ARRAYS_PIVOT_FETCHED(X)), "DEVLU_ARRAYS_PIVOT_HELD + _FETCHED must list every member of DEVLU_ARRAYS_HOT");
+#undef X
+// The view of the wave kernels of a batch (k_pivot_wave.hip, k_pivot_wave2.inc): every hot array and every scalar held.
+// The diet below was measured on them too: the batch of 10k-size bases (k_pivot_loop_wave) got faster, the batch of
+// 50k-size bases (k_pivot_loop_wave2) 1.4 % slower, so they stay as they were.
 struct DevGP {
 #define X(T, n) T n;
     DEVLU_SCALARS(X)
@@ -311,6 +342,44 @@ struct DevGP {
     {
     }
 };
+// The view of k_pivot_loop (one basis, sixteen waves): see ColdVal and DEVLU_ARRAYS_PIVOT_FETCHED above;
+// k_pivot_view.h names it DevGP inside the namespace of that kernel.
+struct DevGPDiet {
+#define X(T, n) T n;
+    DEVLU_SCALARS_HELD(X)
+#undef X
+#define X(T, n) ColdVal<T> n;
+    DEVLU_SCALARS_COLD(X)
+#undef X
+#define X(T, n) GPTR(T) n;
+    DEVLU_ARRAYS_PIVOT_HELD(X)
+#undef X
+#define X(T, n) ColdArr<T> n;
+    DEVLU_ARRAYS_PIVOT_FETCHED(X)
+    DEVLU_ARRAYS_COLD(X)
+#undef X
+    Scalars *s;
+    DEV_LINE_VIEWS
+    __device__ __forceinline__ explicit DevGPDiet(const DevLU *d)
+        :
+#define X(T, n) n(d->n),
+          DEVLU_SCALARS_HELD(X)
+#undef X
+#define X(T, n) n{(const __attribute__((address_space(4))) T *)&d->n},
+          DEVLU_SCALARS_COLD(X)
+#undef X
+#define X(T, n) n((GPTR(T))d->n),
+              DEVLU_ARRAYS_PIVOT_HELD(X)
+#undef X
+#define X(T, n) n{(const __attribute__((address_space(1))) ColdArr<T>::ptr_t *)&d->n},
+                  DEVLU_ARRAYS_PIVOT_FETCHED(X)
+                  DEVLU_ARRAYS_COLD(X)
+#undef X
+                      s(d->s),
+          DEV_LINE_VIEWS_INIT
+    {
+    }
+};
 
 // ---------------------------------------------------------------------------------------------
 // wave64 primitives
@@ -318,6 +387,21 @@ struct DevGP {
 __device__ __forceinline__ int lane_id() { return threadIdx.x & 63; }
 __device__ __forceinline__ int wave_id() { return threadIdx.x >> 6; }
 __device__ __forceinline__ int num_waves() { return blockDim.x >> 6; }
+
+// A lane predicate that does not change over a loop (lane == 0 above all) is computed once in front of the loop and kept
+// as a 64-bit mask in a scalar pair; in the pivot kernels that pair is spilled into a VGPR lane and comes back with two
+// v_readlane and a wait state at every use, where the compare itself is one instruction.  uniform_here(x) is x behind an
+// optimisation barrier (no instruction): what is computed from it is computed where it is used.
+#ifdef BLU_EMU_BUILD
+__device__ __forceinline__ int uniform_here(int x) { return x; }
+#else
+__device__ __forceinline__ int uniform_here(int x)
+{
+    asm volatile("" : "+s"(x));
+    return x;
+}
+#endif
+// (lane_is0 of k_pivot_loop: k_pivot_view.h)
 
 __device__ __forceinline__ unsigned long long lanes_below(int lane) { return (1ull << lane) - 1ull; }
 // number of set bits of a ballot below THIS lane: v_mbcnt_lo / v_mbcnt_hi, two instructions (the shift-mask-popcount

@@ -24,7 +24,7 @@
 //   pv_wave     k_pivot_loop_wave, _wave_r3          a batch of matrices, one wave each (BLU_CFG_WAVE 1, k_pivot_wave.hip)
 //   pv_wave2    k_pivot_loop_wave2, _wave2_r3        a batch of matrices, two waves each (BLU_CFG_WAVE 2)
 namespace BLU_NS {
-
+#include "k_pivot_view.h" // DevGP and lane_is0 of this kernel family
 // A failed check also raises this LDS flag, so the pivot loop can stop at the next pivot boundary
 // without polling the status word in HBM every iteration.
 __shared__ int g_pivot_err;
@@ -254,7 +254,7 @@ __device__ COLD void markowitz_wave(const DevGP &D, Sm *sm)
 
     const int h0 = D.cflink[m];
     if (h0 != m) { // empty column in the active submatrix: chosen immediately (markowitz.rs:73-78)
-        if (lane == 0) {
+        if (LANE_IS0(lane)) {
             sm->pc = h0;
             sm->pr = -1;
         }
@@ -318,7 +318,7 @@ __device__ COLD void markowitz_wave(const DevGP &D, Sm *sm)
         }
         if (!done) nz++;
     }
-    if (lane == 0) {
+    if (LANE_IS0(lane)) {
         sm->pr = best_r;
         sm->pc = best_c;
         sm->nsearch += nsearch;
@@ -520,7 +520,7 @@ __device__ __forceinline__ void gen_update_col(const DevGP &D, Sm *sm, int q, bo
     if (reloc) { // file_reappend (file.rs:56-85): move the line to fresh space at the arena end
         newcap = need_max + stretch_of(D.stretch, need_max) + D.pad;
         int nb = 0;
-        if (lane == 0) nb = atomicAdd(&sm->cused, newcap);
+        if (LANE_IS0(lane)) nb = atomicAdd(&sm->cused, newcap);
         dst = __shfl(nb, 0);
     }
     // pass 2: compress kept entries; kept[0] goes where the pivot-row entry was (the swap of
@@ -554,7 +554,7 @@ __device__ __forceinline__ void gen_update_col(const DevGP &D, Sm *sm, int q, bo
             nk += __popcll(kb);
         }
     }
-    if (where > 0 && lane == 0) {
+    if (where > 0 && LANE_IS0(lane)) {
         D.cidx[dst + where - 1] = first_idx;
         D.cval[dst + where - 1] = first_val;
     }
@@ -600,7 +600,7 @@ __device__ __forceinline__ void gen_update_col(const DevGP &D, Sm *sm, int q, bo
         nadd = cnz1;
     }
     const double cmx = wave_max_d(cmxl);
-    if (lane == 0) {
+    if (LANE_IS0(lane)) {
         const int newlen = nk1 + nadd;
         D.cbeg[j] = dst;
         D.clen[j] = newlen;
@@ -641,7 +641,7 @@ __device__ __forceinline__ void gen_update_row(const DevGP &D, Sm *sm, int p, bo
     if (reloc) {
         newcap = need_max + stretch_of(D.stretch, need_max) + D.pad;
         int nb = 0;
-        if (lane == 0) nb = atomicAdd(&sm->rused, newcap);
+        if (LANE_IS0(lane)) nb = atomicAdd(&sm->rused, newcap);
         dst = __shfl(nb, 0);
     }
     int t0 = 0;
@@ -668,7 +668,7 @@ __device__ __forceinline__ void gen_update_row(const DevGP &D, Sm *sm, int p, bo
         if (ok) D.ridx[put + na + wave_prefix_count(kb)] = jq;
         na += __popcll(kb);
     }
-    if (lane == 0) {
+    if (LANE_IS0(lane)) {
         D.rbeg[i] = dst;
         D.rlen[i] = nk + na;
         D.rcap[i] = newcap;
@@ -696,7 +696,7 @@ __device__ __forceinline__ void wave_write_u(const DevGP &D, Sm *sm, int q0, int
         }
         put += __popcll(kb);
     }
-    if (lane == 0) {
+    if (LANE_IS0(lane)) {
         D.ubeg[sm->rank + 1] = put;
         sm->uused = put;
     }
@@ -722,7 +722,7 @@ __device__ __forceinline__ void wave_write_l(const DevGP &D, Sm *sm, int p0, int
         }
         put += __popcll(kb);
     }
-    if (lane == 0) {
+    if (LANE_IS0(lane)) {
         D.lbeg[sm->rank + 1] = put;
         sm->lused = put;
     }
@@ -743,7 +743,7 @@ __device__ COLD bool pivot_general(const DevGP &D, Sm *sm, bool small)
     if (w == 0) {
         const int where = wave_find(D.cidx, pcb, cnz1 + 1, pr);
         DEV_CHECK(S, where >= 0);
-        if (lane == 0 && where >= 0) {
+        if (LANE_IS0(lane) && where >= 0) {
             const int ti = D.cidx[pcb];
             const double tv = D.cval[pcb];
             const double pv = D.cval[where];
@@ -757,7 +757,7 @@ __device__ COLD bool pivot_general(const DevGP &D, Sm *sm, bool small)
     if (w == (nw > 1 ? 1 : 0)) {
         const int where = wave_find(D.ridx, prb, rnz1 + 1, pc);
         DEV_CHECK(S, where >= 0);
-        if (lane == 0 && where >= 0) {
+        if (LANE_IS0(lane) && where >= 0) {
             const int tj = D.ridx[prb];
             D.ridx[prb] = pc;
             D.ridx[where] = tj;
@@ -813,10 +813,10 @@ __device__ COLD bool pivot_general(const DevGP &D, Sm *sm, bool small)
     if (w == 0) wave_write_u(D, sm, 1, rnz1, -1);
     if (w == 1 % nw) wave_write_l(D, sm, 1, cnz1, -1);
     if (w == 2 % nw) {
-        if (lane == 0) list_remove1(D.cflink, D.cblink, pc);
+        if (LANE_IS0(lane)) list_remove1(D.cflink, D.cblink, pc);
         wave_mem_sync();
         const int mn = wave_list_move_batch(D.cflink, D.cblink, m, D.ridx + prb + 1, D.tnew + 1, rnz1, D.iw2, m + 2);
-        if (lane == 0 && mn < sm->min_colnz) sm->min_colnz = mn;
+        if (LANE_IS0(lane) && mn < sm->min_colnz) sm->min_colnz = mn;
     }
     for (int p = 1 + w; p <= cnz1; p += nw) gen_update_row(D, sm, p, small);
     __syncthreads();
@@ -825,10 +825,10 @@ __device__ COLD bool pivot_general(const DevGP &D, Sm *sm, bool small)
     for (int p = 1 + tid; p <= cnz1; p += nt) D.rowmark[D.cidx[pcb + p]] = 0;
     for (int q = tid; q <= rnz1; q += nt) D.colmark[D.ridx[prb + q]] = 0;
     if (D.search_rows && w == 0) {
-        if (lane == 0) list_remove1(D.rflink, D.rblink, pr);
+        if (LANE_IS0(lane)) list_remove1(D.rflink, D.rblink, pr);
         wave_mem_sync();
         const int mn = wave_list_move_batch(D.rflink, D.rblink, m, D.cidx + pcb + 1, D.tnewr + 1, cnz1, D.iw2, m + 2);
-        if (lane == 0 && mn < sm->min_rownz) sm->min_rownz = mn;
+        if (LANE_IS0(lane) && mn < sm->min_rownz) sm->min_rownz = mn;
     }
     if (tid == 0) {
         D.colmax[pc] = sm->pivot;
@@ -853,7 +853,7 @@ __device__ COLD bool pivot_singleton_row(const DevGP &D, Sm *sm)
     if (w == 0) {
         const int where = wave_find(D.cidx, pcb, cl, pr);
         DEV_CHECK(S, where >= 0);
-        if (lane == 0) {
+        if (LANE_IS0(lane)) {
             sm->where = where - pcb;
             sm->pivot = where >= 0 ? D.cval[where] : 1.0;
         }
@@ -864,7 +864,7 @@ __device__ COLD bool pivot_singleton_row(const DevGP &D, Sm *sm)
     // L column in column order, pivot skipped; U row empty
     if (w == 0) {
         wave_write_l(D, sm, 0, cl - 1, wherep);
-        if (lane == 0) D.ubeg[sm->rank + 1] = sm->uused;
+        if (LANE_IS0(lane)) D.ubeg[sm->rank + 1] = sm->uused;
     }
     // remove the pivot column from the row file: last entry moves into the hole (pivot.rs:902-903)
     for (int p = w; p < cl; p += nw) {
@@ -873,7 +873,7 @@ __device__ COLD bool pivot_singleton_row(const DevGP &D, Sm *sm)
         const int rb = D.rbeg[i], rl = D.rlen[i];
         const int where = wave_find(D.ridx, rb, rl, pc);
         DEV_CHECK(S, where >= 0);
-        if (lane == 0 && where >= 0) {
+        if (LANE_IS0(lane) && where >= 0) {
             D.ridx[where] = D.ridx[rb + rl - 1];
             D.rlen[i] = rl - 1;
             D.tnewr[p] = rl - 1;
@@ -882,14 +882,14 @@ __device__ COLD bool pivot_singleton_row(const DevGP &D, Sm *sm)
     if (tid == 0) D.tnewr[wherep] = -1;
     __syncthreads();
     if (w == 0) {
-        if (lane == 0) list_remove1(D.cflink, D.cblink, pc);
+        if (LANE_IS0(lane)) list_remove1(D.cflink, D.cblink, pc);
         if (D.search_rows) {
-            if (lane == 0) list_remove1(D.rflink, D.rblink, pr);
+            if (LANE_IS0(lane)) list_remove1(D.rflink, D.rblink, pr);
             wave_mem_sync();
             const int mn = wave_list_move_batch(D.rflink, D.rblink, m, D.cidx + pcb, D.tnewr, cl, D.iw2, m + 2);
-            if (lane == 0 && mn < sm->min_rownz) sm->min_rownz = mn;
+            if (LANE_IS0(lane) && mn < sm->min_rownz) sm->min_rownz = mn;
         }
-        if (lane == 0) {
+        if (LANE_IS0(lane)) {
             D.colmax[pc] = sm->pivot;
             D.clen[pc] = 0;
             D.rlen[pr] = 0;
@@ -918,7 +918,7 @@ __device__ COLD bool pivot_singleton_col(const DevGP &D, Sm *sm)
     for (int q = w; q < rl; q += nw) {
         const int j = D.ridx[prb + q];
         if (j == pc) {
-            if (lane == 0) {
+            if (LANE_IS0(lane)) {
                 D.tnew[q] = -1;
                 sm->where = q;
             }
@@ -945,7 +945,7 @@ __device__ COLD bool pivot_singleton_col(const DevGP &D, Sm *sm)
         }
         DEV_CHECK(S, where >= 0);
         const double cmx = wave_max_d(cmxl);
-        if (lane == 0 && where >= 0) {
+        if (LANE_IS0(lane) && where >= 0) {
             D.cidx[cb + where] = D.cidx[cb + cl - 1]; // last entry into the hole (pivot.rs:991-993)
             D.cval[cb + where] = D.cval[cb + cl - 1];
             D.clen[j] = cl - 1;
@@ -959,13 +959,13 @@ __device__ COLD bool pivot_singleton_col(const DevGP &D, Sm *sm)
     DEV_CHECK(S, sm->pivot != 0.0);
     if (w == 0) {
         wave_write_u(D, sm, 0, rl - 1, sm->where);
-        if (lane == 0) D.lbeg[sm->rank + 1] = sm->lused; // empty column in L
+        if (LANE_IS0(lane)) D.lbeg[sm->rank + 1] = sm->lused; // empty column in L
     }
     if (w == 1 % nw) {
-        if (lane == 0) list_remove1(D.cflink, D.cblink, pc);
+        if (LANE_IS0(lane)) list_remove1(D.cflink, D.cblink, pc);
         wave_mem_sync();
         const int mn = wave_list_move_batch(D.cflink, D.cblink, m, D.ridx + prb, D.tnew, rl, D.iw2, m + 2);
-        if (lane == 0) {
+        if (LANE_IS0(lane)) {
             if (mn < sm->min_colnz) sm->min_colnz = mn;
             if (D.search_rows) list_remove1(D.rflink, D.rblink, pr);
             D.colmax[pc] = sm->pivot;
@@ -990,7 +990,7 @@ __device__ COLD bool pivot_doubleton_col(const DevGP &D, Sm *sm)
 
     // pivot to the front of the pivot column (2 entries) and of the pivot row (pivot.rs:1069-1086)
     if (w == 0) {
-        if (lane == 0) {
+        if (LANE_IS0(lane)) {
             if (D.cidx[pcb] != pr) {
                 const int ti = D.cidx[pcb];
                 const double tv = D.cval[pcb];
@@ -1010,7 +1010,7 @@ __device__ COLD bool pivot_doubleton_col(const DevGP &D, Sm *sm)
     if (w == (nw > 1 ? 1 : 0)) {
         const int where = wave_find(D.ridx, prb, rnz1 + 1, pc);
         DEV_CHECK(S, where >= 0);
-        if (lane == 0 && where >= 0) {
+        if (LANE_IS0(lane) && where >= 0) {
             const int tj = D.ridx[prb];
             D.ridx[prb] = pc;
             D.ridx[where] = tj;
@@ -1066,7 +1066,7 @@ __device__ COLD bool pivot_doubleton_col(const DevGP &D, Sm *sm)
         }
         DEV_CHECK(S, where_pivot >= 0);
         double cmx = wave_max_d(cmxl);
-        if (lane == 0 && where_pivot >= 0) {
+        if (LANE_IS0(lane) && where_pivot >= 0) {
             int newkey = -1;
             unsigned long long flags = 0;
             if (where_other < 0) {
@@ -1117,10 +1117,10 @@ __device__ COLD bool pivot_doubleton_col(const DevGP &D, Sm *sm)
     // U row; column count lists
     if (w == 0) wave_write_u(D, sm, 1, rnz1, -1);
     if (w == 1 % nw) {
-        if (lane == 0) list_remove1(D.cflink, D.cblink, pc);
+        if (LANE_IS0(lane)) list_remove1(D.cflink, D.cblink, pc);
         wave_mem_sync();
         const int mn = wave_list_move_batch(D.cflink, D.cblink, m, D.ridx + prb + 1, D.tnew + 1, rnz1, D.iw2, m + 2);
-        if (lane == 0 && mn < sm->min_colnz) sm->min_colnz = mn;
+        if (LANE_IS0(lane) && mn < sm->min_colnz) sm->min_colnz = mn;
     }
     // row file update of the other row (pivot.rs:1224-1293), ONE wave
     if (w == 2 % nw) {
@@ -1144,7 +1144,7 @@ __device__ COLD bool pivot_doubleton_col(const DevGP &D, Sm *sm)
         } else { // last entry into the hole
             const int where = wave_find(D.ridx, rb, rl, pc);
             DEV_CHECK(S, where >= 0);
-            if (lane == 0 && where >= 0) D.ridx[where] = D.ridx[rb + rl - 1];
+            if (LANE_IS0(lane) && where >= 0) D.ridx[where] = D.ridx[rb + rl - 1];
             rl--;
             wave_mem_sync();
         }
@@ -1158,14 +1158,14 @@ __device__ COLD bool pivot_doubleton_col(const DevGP &D, Sm *sm)
         if (rl + nfill > newcap) {
             newcap = rl + nfill + stretch_of(D.stretch, rl + nfill) + D.pad;
             int nb = 0;
-            if (lane == 0) nb = atomicAdd(&sm->rused, newcap);
+            if (LANE_IS0(lane)) nb = atomicAdd(&sm->rused, newcap);
             nb = __shfl(nb, 0);
             for (int c = 0; c < rl; c += 64) {
                 const int e = c + lane;
                 if (e < rl) D.ridx[nb + e] = D.ridx[rb + e];
             }
             rb = nb;
-            if (lane == 0) sm->nexpand++;
+            if (LANE_IS0(lane)) sm->nexpand++;
         }
         int na = 0;
         for (int c = 0; c < rnz1; c += 64) {
@@ -1175,7 +1175,7 @@ __device__ COLD bool pivot_doubleton_col(const DevGP &D, Sm *sm)
             if (ok) D.ridx[rb + rl + na + wave_prefix_count(kb)] = D.ridx[prb + q];
             na += __popcll(kb);
         }
-        if (lane == 0) {
+        if (LANE_IS0(lane)) {
             D.rbeg[other_row] = rb;
             D.rlen[other_row] = rl + na;
             D.rcap[other_row] = newcap;
@@ -1402,7 +1402,7 @@ __device__ __forceinline__ void pivot_loop_body(DevLU *Ds, int stop_at, Sm *sm, 
     for (;;) {
         if (w == 0) {
             // ---- loop head: done / stop / error?
-            if (lane == 0) {
+            if (LANE_IS0(lane)) {
                 if (g_pivot_err) sm->exit_code = ST_ERROR;
                 else if (sm->rank + sm->rankdef >= m) sm->exit_code = ST_DONE;
                 else if (sm->stop_at >= 0 && sm->pc < 0 && sm->rank + sm->rankdef >= sm->stop_at) sm->exit_code = ST_STOPPED;
@@ -1428,11 +1428,11 @@ __device__ __forceinline__ void pivot_loop_body(DevLU *Ds, int stop_at, Sm *sm, 
                     if (D.search_rows == 0 && !D.no_fast) handled = markowitz_fast(D, sm, mc, ew_mcb, ew_fb);
                     if (!handled) {
                         if (D.search_rows == 0) markowitz_wave(D, sm);
-                        else if (lane == 0) markowitz_serial(D, sm);
+                        else if (LANE_IS0(lane)) markowitz_serial(D, sm);
                         wave_mem_sync();
                     }
                 }
-                if (!handled && lane == 0) setup_pivot_general(D, sm);
+                if (!handled && LANE_IS0(lane)) setup_pivot_general(D, sm);
             }
         }
         __syncthreads();

@@ -419,7 +419,7 @@ __device__ __forceinline__ int wave_list_move_batch_set(const Links &L, int nele
         return minall; // no drain here: the workgroup barrier that follows waits for the stores
     }
     if (gone >= 0) { // long batches: unlink `gone` first, as the general path does
-        if (lane == 0) { // list_remove1 through the accessor
+        if (lane_is0(lane)) { // list_remove1 through the accessor
             const int f = L.fl(gone), b = L.bl(gone);
             L.set_fl(b, f);
             L.set_bl(f, b);
@@ -498,7 +498,7 @@ __device__ __forceinline__ int mk_walk(const DevGP &D, Sm *sm, Mc *mc)
     const LinksC LC{D, mc};
     const int h0 = LC.fl(m);
     if (h0 != m) { // empty column: chosen immediately (markowitz.rs:73-78)
-        if (lane == 0) {
+        if (lane_is0(lane)) {
             sm->pc = h0;
             sm->pr = -1;
         }
@@ -549,7 +549,7 @@ __device__ __forceinline__ int mk_walk(const DevGP &D, Sm *sm, Mc *mc)
                     bad = true;
                     break;
                 }
-                if (lane == 0) {
+                if (lane_is0(lane)) {
                     fa->cJ[ncand] = j;
                     fa->cNz[ncand] = znz;
                     fa->cB[ncand] = cb;
@@ -566,13 +566,13 @@ __device__ __forceinline__ int mk_walk(const DevGP &D, Sm *sm, Mc *mc)
     }
     if (bad || ncand == 0) { // reference: assert / D2 / "no pivot found" assert
         DEV_CHECK(S, false);
-        if (lane == 0) {
+        if (lane_is0(lane)) {
             sm->pc = -1;
             sm->pr = -1;
         }
         return 2;
     }
-    if (lane == 0) {
+    if (lane_is0(lane)) {
         fa->cOff[ncand] = total;
         fa->ncand = ncand;
     }
@@ -683,7 +683,7 @@ __device__ __forceinline__ bool mk_express(const DevGP &D, Sm *sm, Mc *mc, int &
     if (x == 0.0 || x < tol) return false;
     const int left = m - sm->rank - sm->rankdef; // every active column is in a count list, list 0 is empty
     nsearched = left < K ? left : K;
-    if (lane == 0) {
+    if (lane_is0(lane)) {
         fa->ncand = 1;
         fa->cJ[0] = j;
         fa->cNz[0] = 1;
@@ -713,13 +713,13 @@ __device__ __forceinline__ void mk_pick(const DevGP &D, Sm *sm, long long mcb, i
     const int off1 = ncand > 1 ? fa->cOff[1] : 0x7fffffff, off2 = ncand > 2 ? fa->cOff[2] : 0x7fffffff,
               off3 = ncand > 3 ? fa->cOff[3] : 0x7fffffff;
     const long long BIG = 0x7fffffffffffffffLL;
-    if (lane == 0) fa->kind = 0;
+    if (lane_is0(lane)) fa->kind = 0;
     // key = cost * 256 + position (position < STGMAX <= 256, cost < 2^55); first-seen entry wins ties
     const long long bestkey = key_given >= 0 ? key_given : (single ? 0LL : wave_min_ll(mcb != BIG ? mcb * 256LL + (long long)fb : BIG));
     wave_mem_sync();
     if (bestkey == BIG) { // no eligible entry: cannot happen when colmax is the column maximum
         DEV_CHECK(S, false);
-        if (lane == 0) {
+        if (lane_is0(lane)) {
             sm->pc = -1;
             sm->pr = -1;
         }
@@ -730,7 +730,7 @@ __device__ __forceinline__ void mk_pick(const DevGP &D, Sm *sm, long long mcb, i
     const int pc = fa->cJ[csel], pr = fa->sI[fsel];
     const int nzc = fa->cL[csel], pcb = fa->cB[csel], where = fsel - fa->cOff[csel];
     const int nzr = fa->sL[fsel], prb = fa->sB[fsel];
-    if (lane == 0) {
+    if (lane_is0(lane)) {
         sm->pr = pr;
         sm->pc = pc;
         sm->pcb = pcb;
@@ -786,7 +786,7 @@ __device__ __forceinline__ void mk_pick(const DevGP &D, Sm *sm, long long mcb, i
         const unsigned long long hb = __ballot(jq0 == pc);
         if (!hb) {
             DEV_CHECK(S, false);
-            if (lane == 0) sm->pc = -1;
+            if (lane_is0(lane)) sm->pc = -1;
             return;
         }
         const int wpos = __ffsll((long long)hb) - 1;
@@ -826,7 +826,7 @@ __device__ __forceinline__ void mk_pick(const DevGP &D, Sm *sm, long long mcb, i
             if ((long long)sm->cused + (both >> 32) > (long long)D.carena_cap || (long long)sm->rused + (both & 0xffffffffLL) > (long long)D.rarena_cap)
                 kind = 0; // the general path makes the exact check and leaves with NEED_CW / NEED_RW
         }
-        if (lane == 0) {
+        if (lane_is0(lane)) {
             fa->kind = kind;
             fa->where = wpos;
             fa->tLnk = 1;
@@ -884,7 +884,7 @@ __device__ __forceinline__ void mk_pick(const DevGP &D, Sm *sm, long long mcb, i
     }
     if (wpos < 0) {
         DEV_CHECK(S, false);
-        if (lane == 0) sm->pc = -1;
+        if (lane_is0(lane)) sm->pc = -1;
         return;
     }
     PROF_STAMP(12); // pivot column copied, pivot row loaded
@@ -939,7 +939,7 @@ __device__ __forceinline__ void mk_pick(const DevGP &D, Sm *sm, long long mcb, i
         if ((long long)sm->cused + gc > (long long)D.carena_cap || (long long)sm->rused + gr > (long long)D.rarena_cap)
             kind = 0; // the general path makes the exact check and leaves with NEED_CW / NEED_RW
     }
-    if (lane == 0) {
+    if (lane_is0(lane)) {
         fa->kind = kind;
         fa->where = wpos;
         fa->tLnk = 0;
@@ -963,7 +963,7 @@ __device__ __forceinline__ bool markowitz_fast(const DevGP &D, Sm *sm, Mc *mc, l
         const int fb = ew_fb;
         nsr = fa->ewNsr;
         wave_mem_sync();
-        if (lane == 0) {
+        if (lane_is0(lane)) {
             if (!whole) sm->nrun[0]++;
             fa->ewValid = 0;
         }
@@ -1009,7 +1009,7 @@ __device__ __forceinline__ bool markowitz_fast(const DevGP &D, Sm *sm, Mc *mc, l
             }
             okc = okc && fa->ncand == sN && nsr2 == nsr && mcb2 == mcb && fb2 == fb && (lane >= sN || fa->cJ[lane] == myc);
             if (__ballot(!okc)) {
-                if (lane == 0 && D.s->prof[0] == 0) {
+                if (lane_is0(lane) && D.s->prof[0] == 0) {
                     long long *P = D.s->prof;
                     P[0] = 1 + sm->rank;
                     P[1] = sN * 10 + fa->ncand;
@@ -1105,7 +1105,7 @@ __device__ __forceinline__ void fast_col(const DevGP &D, Sm *sm, Mc *mc, Fast *f
     if (reloc) {
         newcap = need_max + stretch_of(D.stretch, need_max) + D.pad;
         int nb = 0;
-        if (lane == 0) nb = atomicAdd(&sm->cused, newcap);
+        if (lane_is0(lane)) nb = atomicAdd(&sm->cused, newcap);
         dst = __builtin_amdgcn_readfirstlane(nb);
     }
     if (cl <= 64) {
@@ -1130,7 +1130,7 @@ __device__ __forceinline__ void fast_col(const DevGP &D, Sm *sm, Mc *mc, Fast *f
             nk += __popcll(kb);
         }
     }
-    if (where > 0 && lane == 0) {
+    if (where > 0 && lane_is0(lane)) {
         D.cidx[dst + where - 1] = first_idx;
         D.cval[dst + where - 1] = first_val;
     }
@@ -1158,7 +1158,7 @@ __device__ __forceinline__ void fast_col(const DevGP &D, Sm *sm, Mc *mc, Fast *f
     // column maximum: LDS atomic max on the bit patterns (non-negative doubles order like integers);
     // one LDS round trip instead of a 6-step cross-lane reduction
     const double cmx = wave_max_d(cmxl);
-    if (lane == 0) {
+    if (lane_is0(lane)) {
         const int newlen = nk1 + nadd;
         D.cbeg[j] = dst;
         D.clen[j] = newlen;
@@ -1220,14 +1220,14 @@ __device__ __forceinline__ void fast_col_short(const DevGP &D, Sm *sm, Mc *mc, F
     if (reloc) {
         newcap = need_max + stretch_of(D.stretch, need_max) + D.pad;
         int nb = 0;
-        if (lane == 0) nb = atomicAdd(&sm->cused, newcap);
+        if (lane_is0(lane)) nb = atomicAdd(&sm->cused, newcap);
         dst = __builtin_amdgcn_readfirstlane(nb);
     }
     if (keep && t != where && t > 0) {
         D.cidx[dst + t - 1] = idx;
         D.cval[dst + t - 1] = val;
     }
-    if (where > 0 && lane == 0) {
+    if (where > 0 && lane_is0(lane)) {
         D.cidx[dst + where - 1] = first_idx;
         D.cval[dst + where - 1] = first_val;
     }
@@ -1256,7 +1256,7 @@ __device__ __forceinline__ void fast_col_short(const DevGP &D, Sm *sm, Mc *mc, F
     unsigned long long *wm = &sm->wmax[wave_id()];
     if (cmxl > 0.0) atomicMax(wm, (unsigned long long)__double_as_longlong(cmxl));
     wave_mem_sync();
-    if (lane == 0) {
+    if (lane_is0(lane)) {
         const double cmx = __longlong_as_double((long long)*wm);
         *wm = 0ull;
         const int newlen = nk1 + __popcll(kxb);
@@ -1312,7 +1312,7 @@ __device__ __forceinline__ void fast_row(const DevGP &D, Sm *sm, Fast *fa, int p
     if (reloc) {
         newcap = need_max + stretch_of(D.stretch, need_max) + D.pad;
         int nb = 0;
-        if (lane == 0) nb = atomicAdd(&sm->rused, newcap);
+        if (lane_is0(lane)) nb = atomicAdd(&sm->rused, newcap);
         dst = __builtin_amdgcn_readfirstlane(nb);
     }
     if (rl <= 64) {
@@ -1330,7 +1330,7 @@ __device__ __forceinline__ void fast_row(const DevGP &D, Sm *sm, Fast *fa, int p
         }
     }
     for (int q = 1 + lane; q <= rnz1; q += 64) D.ridx[dst + nk + q - 1] = fa->tJ[q];
-    if (lane == 0) {
+    if (lane_is0(lane)) {
         D.rbeg[i] = dst;
         D.rlen[i] = nk + rnz1;
         D.rcap[i] = newcap;
@@ -1368,12 +1368,12 @@ __device__ __forceinline__ void fast_row_short(const DevGP &D, Sm *sm, Fast *fa,
     if (reloc) {
         newcap = need_max + stretch_of(D.stretch, need_max) + D.pad;
         int nb = 0;
-        if (lane == 0) nb = atomicAdd(&sm->rused, newcap);
+        if (lane_is0(lane)) nb = atomicAdd(&sm->rused, newcap);
         dst = __builtin_amdgcn_readfirstlane(nb);
     }
     if (keep) D.ridx[dst + t0] = j;
     for (int q = 1 + lane; q <= rnz1; q += 64) D.ridx[dst + nk + q - 1] = fa->tJ[q];
-    if (lane == 0) {
+    if (lane_is0(lane)) {
         D.rbeg[i] = dst;
         D.rlen[i] = nk + rnz1;
         D.rcap[i] = newcap;
@@ -1407,7 +1407,7 @@ __device__ __forceinline__ void fast_fixrow(const DevGP &D, Fast *fa, int p, int
         if (ok) D.ridx[dst + nk + na + wave_prefix_count(kb)] = fa->tJ[q];
         na += __popcll(kb);
     }
-    if (lane == 0) {
+    if (lane_is0(lane)) {
         D.rlen[fa->pcI[p]] = nk + na;
         fa->rNew[p] = nk + na;
     }
@@ -1442,7 +1442,7 @@ __device__ __forceinline__ void fast_write_u(const DevGP &D, Sm *sm, const Fast 
         }
         put += __popcll(kb);
     }
-    if (lane == 0) {
+    if (lane_is0(lane)) {
         D.ubeg[sm->rank + 1] = put;
         sm->uused = put;
     }
@@ -1467,7 +1467,7 @@ __device__ __forceinline__ void fast_write_l(const DevGP &D, Sm *sm, const Fast 
         }
         put += __popcll(kb);
     }
-    if (lane == 0) {
+    if (lane_is0(lane)) {
         D.lbeg[sm->rank + 1] = put;
         sm->lused = put;
     }
@@ -1550,7 +1550,7 @@ __device__ __forceinline__ void early_search(const DevGP &D, Sm *sm, Mc *mc, con
             // (Tried on the route without a round trip, fs >= 0: the load of the pivot row issued here from registers, ahead of the
             // staging stores and the fence, and pc / pr / prb / nzr handed to scol_setup_next in registers: 693.8 -> 694.6 ms per
             // step, third library in the rotation of profiles/setup_split_ab.txt.  Not kept.)
-            if (lane == 0) {
+            if (lane_is0(lane)) {
                 fa->ncand = 1;
                 fa->cJ[0] = j;
                 fa->cNz[0] = 1;
@@ -1614,7 +1614,7 @@ __device__ __forceinline__ void spec_walk(const DevGP &D, Sm *sm, Mc *mc)
     const int m = D.m;
     Fast *fa = &sm->fa;
     const int K = D.maxsearch;
-    if (lane == 0) fa->spOk = 0;
+    if (lane_is0(lane)) fa->spOk = 0;
     if (D.no_fast || K < 1 || K > KCMAX || m >= (1 << 27)) return;
     if (m - (sm->rank + 1) - sm->rankdef < K) return;
     const LinksC LC{D, mc};
@@ -1641,7 +1641,7 @@ __device__ __forceinline__ void spec_walk(const DevGP &D, Sm *sm, Mc *mc)
                     bad = true;
                     break;
                 }
-                if (lane == 0) {
+                if (lane_is0(lane)) {
                     fa->cJ[ncand] = j;
                     fa->cNz[ncand] = znz;
                     fa->cB[ncand] = cb;
@@ -1659,7 +1659,7 @@ __device__ __forceinline__ void spec_walk(const DevGP &D, Sm *sm, Mc *mc)
     }
     if (bad || ncand < K || total > STGMAX) return;
     SPEC_STAT(1);
-    if (lane == 0) {
+    if (lane_is0(lane)) {
         fa->cOff[ncand] = total;
         fa->ncand = ncand;
         fa->spLastNz = lastnz;
@@ -1750,7 +1750,7 @@ __device__ __forceinline__ void spec_finish(const DevGP &D, Sm *sm, const Fast *
                 fa->cMx[posM] = cs->tMx[1 + lane];
             }
             wave_mem_sync();
-            if (lane == 0) {
+            if (lane_is0(lane)) {
                 int off = 0;
                 for (int i = 0; i < ncand; i++) {
                     fa->cOff[i] = off;
@@ -1956,7 +1956,7 @@ __device__ __forceinline__ void fast_small(const DevGP &D, Sm *sm, Mc *mc, Fast 
 #endif
     // the hand-over words of the two-wave set-up are 0 from the barrier below on: cleared by the wave with the fewest line
     // updates, once it is done with them (their last readers left them before the barrier that ended the previous finalize step)
-    if (early && w == nwt - 1 && lane == 0) {
+    if (early && w == nwt - 1 && lane_is0(lane)) {
         hs_put(&sm->hs_go, 0);
         hs_put(&sm->hs_done, 0);
     }
@@ -1983,19 +1983,19 @@ __device__ __forceinline__ void fast_small(const DevGP &D, Sm *sm, Mc *mc, Fast 
             early_search(D, sm, mc, fa, fa->tJ + 1, fa->tNew + 1, fa->tB + 1, fa->tMx + 1, rnz1, 1, ew_mcb, ew_fb);
             merged = scol_setup_next(D, sm, mc, other, rnz1 + 1); // (the U row of this pivot: at most rnz1 entries)
         }
-        if (lane == 0) sm->mg = merged ? 1 : 0;
+        if (lane_is0(lane)) sm->mg = merged ? 1 : 0;
     }
     if (w == 0 && spec) small_setup_help(D, sm, other);
     if (w == nw - 1 && spec) {
         SpecWin win;
         spec_finish(D, sm, fa, rnz1, win);
         const bool merged = small_setup_next(D, sm, mc, other, cnz1, rnz1, win); // (stamp 45: result published)
-        if (lane == 0) sm->mg = merged ? 1 : 0;
+        if (lane_is0(lane)) sm->mg = merged ? 1 : 0;
         PROF_STAMP_L0(46);
     }
     if (w == (early ? 3 : 0)) {
         fast_write_u(D, sm, fa, 1, rnz1, -1);
-        if (lane == 0) {
+        if (lane_is0(lane)) {
             D.colmax[pc] = fa->pcV[0];
             D.clen[pc] = 0;
             D.rlen[pr] = 0;
@@ -2011,8 +2011,8 @@ __device__ __forceinline__ void fast_small(const DevGP &D, Sm *sm, Mc *mc, Fast 
         PROF_STAMP_L0(25);
         const int mn = split ? wave_list_append_set(LC, m, fa->tJ + 1, fa->tNew + 1, rnz1, m + 2, sm->fa.kg[0], mc->pFl + 1)
                              : wave_list_move_batch_set(LC, m, fa->tJ + 1, fa->tNew + 1, rnz1, InHCol{fa, 1, 0}, m + 2, pc, sm->fa.kg[0]);
-        if (lane == 0 && mn < sm->min_colnz) sm->min_colnz = mn;
-        if (lane == 0) { // (the ordinary search reads the previous pivot from sm->fa only, as in fast_scol)
+        if (lane_is0(lane) && mn < sm->min_colnz) sm->min_colnz = mn;
+        if (lane_is0(lane)) { // (the ordinary search reads the previous pivot from sm->fa only, as in fast_scol)
             mc->prevValid = split && fa == &sm->fa ? 1 : 0;
             mc->prevBase = 1;
         }
@@ -2020,10 +2020,10 @@ __device__ __forceinline__ void fast_small(const DevGP &D, Sm *sm, Mc *mc, Fast 
         PROF_STAMP_L0(29);
     }
     if (D.search_rows && w == 3 % nw) {
-        if (lane == 0) list_remove1(D.rflink, D.rblink, pr); // pr is not in the row hash set: unlink it first
+        if (lane_is0(lane)) list_remove1(D.rflink, D.rblink, pr); // pr is not in the row hash set: unlink it first
         wave_mem_sync();
         const int mn = wave_list_move_batch_set(LinksG{D.rflink, D.rblink}, m, fa->pcI + 1, fa->rNew + 1, cnz1, InHRow{fa}, m + 2, -1, sm->fa.kg[1]);
-        if (lane == 0 && mn < sm->min_rownz) sm->min_rownz = mn;
+        if (lane_is0(lane) && mn < sm->min_rownz) sm->min_rownz = mn;
     }
     __syncthreads();
 }
@@ -2072,7 +2072,7 @@ __device__ __forceinline__ bool scol_setup_next(const DevGP &D, Sm *sm, Mc *mc, 
         nxt->tC[lane] = tc;
         hcol_insert(nxt, jq0, lane);
     }
-    if (lane == 0) {
+    if (lane_is0(lane)) {
         nxt->pcI[0] = pr;
         nxt->pcV[0] = st->sV[0];
         nxt->prB[0] = prb;
@@ -2136,7 +2136,7 @@ __device__ __forceinline__ bool small_setup_next(const DevGP &D, Sm *sm, Mc *mc,
     const int lane = lane_id();
     Fast *st = &sm->fa; // where spec_finish stages
     if (win.key < 0) { // spec_finish gave up: nothing published (ewValid stays 0), the helper leaves, the ordinary head searches
-        if (lane == 0) hs_put(&sm->hs_go, 2);
+        if (lane_is0(lane)) hs_put(&sm->hs_go, 2);
         return false;
     }
     // the pivot from the winner in registers; of the candidate only what one round of LDS reads gives
@@ -2163,13 +2163,13 @@ __device__ __forceinline__ bool small_setup_next(const DevGP &D, Sm *sm, Mc *mc,
     // is published and the set-up is under way, 2 = on any way out.  ewValid reads 2 on every way out from here: the ordinary
     // head picks the staged search up.
     const int jq0 = go && lane < nzr ? D.ridx[prb + lane] : -1;
-    if (lane == 0) {
+    if (lane_is0(lane)) {
         st->spKey = win.key;
         st->ewNsr = ncand;
         st->ewValid = 2;
     }
     __builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup"); // (the staged entries of every lane, and the three words above)
-    if (lane == 0) hs_put(&sm->hs_go, go ? 1 : 2);
+    if (lane_is0(lane)) hs_put(&sm->hs_go, go ? 1 : 2);
     PROF_STAMP_L0(45);
     if (!go) return false;
     // ---- the row side, as the straight-line form of mk_pick, on *nxt
@@ -2206,14 +2206,14 @@ __device__ __forceinline__ bool small_setup_next(const DevGP &D, Sm *sm, Mc *mc,
     const int dn = hs_wait(&sm->hs_done);
     __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "workgroup");
     if (dn != 1) { // the helper gave up (it has counted that), or this wait ran out: the ordinary head sets the pivot up
-        if (dn == 0 && lane == 0) atomicAdd((unsigned long long *)&sm->nsplit[1], 1ull);
+        if (dn == 0 && lane_is0(lane)) atomicAdd((unsigned long long *)&sm->nsplit[1], 1ull);
         return false;
     }
     if (kind == 1) {
         if ((long long)sm->cused + gcs > (long long)D.carena_cap || (long long)sm->rused + sm->hs_gr > (long long)D.rarena_cap)
             return false; // mk_pick hands such a pivot to the general path
     }
-    if (lane == 0) {
+    if (lane_is0(lane)) {
         nxt->kind = kind;
         nxt->where = wpos;
         nxt->anycancel = 0;
@@ -2249,7 +2249,7 @@ __device__ __forceinline__ void small_setup_help(const DevGP &D, Sm *sm, Fast *n
     const int go = hs_wait(&sm->hs_go);
     __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "workgroup");
     if (go != 1) {
-        if (go == 0 && lane == 0) {
+        if (go == 0 && lane_is0(lane)) {
             hs_put(&sm->hs_done, 2);
             atomicAdd((unsigned long long *)&sm->nsplit[1], 1ull);
         }
@@ -2279,9 +2279,9 @@ __device__ __forceinline__ void small_setup_help(const DevGP &D, Sm *sm, Fast *n
         }
     }
     const long long grs = wave_sum_ll((long long)gr);
-    if (lane == 0) sm->hs_gr = grs;
+    if (lane_is0(lane)) sm->hs_gr = grs;
     __builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup");
-    if (lane == 0) hs_put(&sm->hs_done, 1);
+    if (lane_is0(lane)) hs_put(&sm->hs_done, 1);
 }
 
 #ifdef BLU_EWCHECK
@@ -2301,7 +2301,7 @@ __device__ __forceinline__ void scol_setup_check(const DevGP &D, Sm *sm, Mc *mc,
         T->tL[lane] = R->tL[lane];
         T->tC[lane] = R->tC[lane];
         for (int s = lane; s < HCOL; s += 64) T->hCol[s] = R->hCol[s];
-        if (lane == 0) {
+        if (lane_is0(lane)) {
             T->kind = R->kind;
             T->where = R->where;
             T->pcI[0] = R->pcI[0];
@@ -2335,7 +2335,7 @@ __device__ __forceinline__ void scol_setup_check(const DevGP &D, Sm *sm, Mc *mc,
         okc = okc && cntR == n && cntT == n;
     }
     wave_mem_sync();
-    if (lane == 0) { // what mk_pick booked for a pivot that is already under way
+    if (lane_is0(lane)) { // what mk_pick booked for a pivot that is already under way
         sm->pr = o_pr;
         sm->pc = o_pc;
         sm->pcb = o_pcb;
@@ -2374,7 +2374,7 @@ __device__ __forceinline__ void small_setup_check(const DevGP &D, Sm *sm, Mc *mc
         T->prC[lane] = R->prC[lane];
         for (int s = lane; s < HCOL; s += 64) T->hCol[s] = R->hCol[s];
         for (int s = lane; s < HROW; s += 64) T->hRow[s] = R->hRow[s];
-        if (lane == 0) {
+        if (lane_is0(lane)) {
             T->kind = R->kind;
             T->where = R->where;
             T->anycancel = R->anycancel;
@@ -2387,7 +2387,7 @@ __device__ __forceinline__ void small_setup_check(const DevGP &D, Sm *sm, Mc *mc
     wave_mem_sync();
     // (the record step has set min_colnz to the early search's first count already: the walk here starts at count 1, so a
     // column of a smaller count that the early search missed would be found)
-    if (lane == 0) sm->min_colnz = 1;
+    if (lane_is0(lane)) sm->min_colnz = 1;
     wave_mem_sync();
     int nsr2 = 0;
     bool okc = true;
@@ -2434,7 +2434,7 @@ __device__ __forceinline__ void small_setup_check(const DevGP &D, Sm *sm, Mc *mc
         }
     }
     wave_mem_sync();
-    if (lane == 0) { // what mk_pick booked for a pivot that is already under way
+    if (lane_is0(lane)) { // what mk_pick booked for a pivot that is already under way
         sm->pr = o_pr;
         sm->pc = o_pc;
         sm->pcb = o_pcb;
@@ -2480,7 +2480,7 @@ __device__ __forceinline__ void fast_scol(const DevGP &D, Sm *sm, Mc *mc, Fast *
     }
     for (int q = w; q < rl && w < nwt; q += nwt) {
         if (q == wq) {
-            if (lane == 0) fa->tNew[q] = -1;
+            if (lane_is0(lane)) fa->tNew[q] = -1;
             continue;
         }
         const int j = fa->tJ[q], cb = fa->tB[q], cl = fa->tL[q];
@@ -2513,7 +2513,7 @@ __device__ __forceinline__ void fast_scol(const DevGP &D, Sm *sm, Mc *mc, Fast *
             const int last_i = wave_bcast_i(idx, cl - 1);
             const double last_v = wave_bcast_d(val, cl - 1);
             wave_mem_sync();
-            if (lane == 0 && hb) {
+            if (lane_is0(lane) && hb) {
                 const double cmx = __longlong_as_double((long long)*wm);
                 *wm = 0ull;
                 D.cidx[cb + src] = last_i;
@@ -2558,7 +2558,7 @@ __device__ __forceinline__ void fast_scol(const DevGP &D, Sm *sm, Mc *mc, Fast *
         }
         DEV_CHECK(S, where >= 0);
         const double cmx = wave_max_d(cmxl);
-        if (lane == 0 && where >= 0) {
+        if (lane_is0(lane) && where >= 0) {
             D.cidx[cb + where] = D.cidx[cb + cl - 1]; // last entry into the hole (pivot.rs:991-993)
             D.cval[cb + where] = D.cval[cb + cl - 1];
             D.clen[j] = cl - 1;
@@ -2580,12 +2580,12 @@ __device__ __forceinline__ void fast_scol(const DevGP &D, Sm *sm, Mc *mc, Fast *
             early_search(D, sm, mc, fa, fa->tJ, fa->tNew, fa->tB, fa->tMx, rl, 0, ew_mcb, ew_fb);
             merged = scol_setup_next(D, sm, mc, fa == &sm->fa ? &sm->fb : &sm->fa, rl);
         }
-        if (lane == 0) sm->mg = merged ? 1 : 0; // read by every wave right after the barrier below
+        if (lane_is0(lane)) sm->mg = merged ? 1 : 0; // read by every wave right after the barrier below
         PROF_STAMP(49);
     }
     if (w == (early ? 2 : 0)) {
         fast_write_u(D, sm, fa, 0, rl - 1, wq);
-        if (lane == 0) {
+        if (lane_is0(lane)) {
             D.lbeg[sm->rank + 1] = sm->lused; // empty column in L
             D.colmax[pc] = fa->pcV[0];
             D.clen[pc] = 0;
@@ -2595,12 +2595,12 @@ __device__ __forceinline__ void fast_scol(const DevGP &D, Sm *sm, Mc *mc, Fast *
         if (w != 0) PROF_STAMP_L0(50);
     }
     if (w == 1 % nw) {
-        if (D.search_rows && lane == 0) list_remove1(D.rflink, D.rblink, pr);
+        if (D.search_rows && lane_is0(lane)) list_remove1(D.rflink, D.rblink, pr);
         // the pivot column sits at slot `where` of the row with key -1: it is unlinked as `gone`
         const int mn = split ? wave_list_append_set(LC, m, fa->tJ, fa->tNew, rl, m + 2, sm->fa.kg[0], mc->pFl)
                              : wave_list_move_batch_set(LC, m, fa->tJ, fa->tNew, rl, InHCol{fa, 0, wq}, m + 2, pc, sm->fa.kg[0]);
-        if (lane == 0 && mn < sm->min_colnz) sm->min_colnz = mn;
-        if (lane == 0) { // what the next search may reuse (a column that sank below abstol cancels it: dirty)
+        if (lane_is0(lane) && mn < sm->min_colnz) sm->min_colnz = mn;
+        if (lane_is0(lane)) { // what the next search may reuse (a column that sank below abstol cancels it: dirty)
             // (the ordinary search reads the previous pivot from sm->fa only: a run that ends on the other set leaves
             // nothing to reuse, and that search -- one per run -- reads memory, which is always current)
             mc->prevValid = split && fa == &sm->fa ? 1 : 0;
