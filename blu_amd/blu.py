@@ -13,6 +13,11 @@ with the same method names, argument meaning and error behaviour:
     .solve_sparse_multi(irhs_list, xrhs_list)      solve_sparse for many right-hand sides on one handle in one call
     .get_sparse_multi(total)                       the compressed solutions the last solve_sparse_multi left in the handle
     .maxvolume(ncol, a_p, a_i, a_x, basis, isbasic, volumetol)   maxvolume, src/maxvolume.rs:64 (one pass, in the library)
+    .set_matrix(ncol, a_p, a_i, a_x)               the rectangular A resident on the device (blu_hip_set_matrix), then
+    .factorize_columns(basis)                      ... factorize A[:, basis] with an m-sized upload
+    .solve_for_update_column(j)                    ... the forward solve_for_update of column j, nothing uploaded
+    .tableau_row(r, prepare_update, skip)          ... row r of B^-1 A: the transposed solve and A' y on the device
+    .price(y, skip)                                ... z = A' y for a dense y
     solve_dense_batch(handles, rhs, trans)         solve_dense for many handles in one call (batch extension)
     solve_for_update_batch(handles, irhs, xrhs)    solve_for_update for many handles in one call (batch extension)
     update_batch(handles, xtbl)                    update for many handles in one call (batch extension)
@@ -51,6 +56,7 @@ EXPORTS = [
     "blu_hip_solve_sparse_batch", "blu_hip_solve_dense_multi",
     "blu_hip_solve_sparse_multi", "blu_hip_get_sparse_multi", "blu_hip_maxvolume",
     "blu_hip_copy_batch", "blu_hip_clone",
+    "blu_hip_set_matrix", "blu_hip_factorize_columns", "blu_hip_solve_for_update_column", "blu_hip_tableau_row", "blu_hip_price",
 ]
 
 
@@ -642,6 +648,118 @@ class BLU:
         lib().blu_hip_dbg_maxvolume_counts.argtypes = [C.c_void_p, C.c_void_p]
         lib().blu_hip_dbg_maxvolume_counts(self._h, out)
         return tuple(int(x) for x in out)
+
+    # --- the resident constraint matrix (blu_matrix.inc) -------------------------------------------------
+    def set_matrix(self, ncol, a_p, a_i, a_x):
+        """Make the rectangular A (ncol compressed columns, every row index below m) resident on the device.  Returns the
+        status; ERROR_DEVICE and ERROR_OUT_OF_MEMORY raise."""
+        ap = np.ascontiguousarray(a_p, dtype=np.uint64)
+        ai = np.ascontiguousarray(a_i, dtype=np.uint64)
+        ax = np.ascontiguousarray(a_x, dtype=np.float64)
+        ncol = int(ncol)
+        if len(ap) != ncol + 1 or len(ai) != len(ax) or (ncol >= 0 and len(ai) < int(ap[-1])):
+            raise ValueError("set_matrix: a_p needs ncol + 1 entries, a_i / a_x a_p[ncol]")
+        L = lib()
+        L.blu_hip_set_matrix.argtypes = [C.c_void_p, C.c_int64] + [C.c_void_p] * 3
+        st = L.blu_hip_set_matrix(self._h, ncol, ap.ctypes.data, ai.ctypes.data if len(ai) else None, ax.ctypes.data if len(ax) else None)
+        if st in (K.ERROR_DEVICE, K.ERROR_OUT_OF_MEMORY):
+            raise BluError(st, self.last_error())
+        if st == K.OK:
+            self._ncol = ncol
+        return st
+
+    def factorize_columns(self, basis):
+        """factorize of A[:, basis] from the resident matrix (m column indices).  Returns the status as factorize does."""
+        b = np.ascontiguousarray(basis, dtype=np.int64)
+        if len(b) != self.m:
+            return K.ERROR_INVALID_ARGUMENT
+        L = lib()
+        L.blu_hip_factorize_columns.argtypes = [C.c_void_p, C.c_void_p]
+        st = L.blu_hip_factorize_columns(self._h, b.ctypes.data or 8)
+        if st in (K.ERROR_DEVICE, K.ERROR_OUT_OF_MEMORY):
+            raise BluError(st, self.last_error())
+        return st
+
+    def solve_for_update_column(self, j, want_solution=True):
+        """solve_for_update(a_i_j, a_x_j, 'N') of column j of the resident matrix; the solution as there."""
+        self._clear_lhs()
+        nz = C.c_int64(0)
+        L = lib()
+        L.blu_hip_solve_for_update_column.argtypes = [C.c_void_p, C.c_int64] + [C.c_void_p] * 3
+        if want_solution:
+            st = L.blu_hip_solve_for_update_column(self._h, int(j), C.addressof(nz), self.ilhs.ctypes.data, self.lhs.ctypes.data or 8)
+        else:
+            st = L.blu_hip_solve_for_update_column(self._h, int(j), None, None, None)
+        if st == K.OK and want_solution:
+            self.nzlhs = int(nz.value)
+        elif st in (K.ERROR_DEVICE, K.ERROR_OUT_OF_MEMORY):
+            raise BluError(st, self.last_error())
+        return st
+
+    def _skip(self, skip, what):
+        if skip is None:
+            return None
+        sk = np.ascontiguousarray(skip, dtype=np.int64)
+        if len(sk) != getattr(self, "_ncol", -1):
+            raise ValueError(what + ": skip needs ncol entries")
+        return sk
+
+    def tableau_row(self, r, prepare_update=False, skip=None, want_solution=False):
+        """Row r of B^-1 A for the resident matrix: (status, alpha) with alpha[j] = A[:, j] . (B^-T e_r), +0.0 where
+        skip[j] != 0.  The transposed solve is solve_sparse([r], [1.0], 'T'), or with prepare_update the transposed
+        solve_for_update([r]); with want_solution its solution is left in self.lhs / self.ilhs[0..nzlhs) as the solves
+        leave it."""
+        ncol = getattr(self, "_ncol", 0)
+        alpha = np.zeros(ncol)
+        sk = self._skip(skip, "tableau_row")
+        nz = C.c_int64(0)
+        L = lib()
+        L.blu_hip_tableau_row.argtypes = [C.c_void_p, C.c_int64, C.c_int] + [C.c_void_p] * 5
+        if want_solution:
+            self._clear_lhs()
+            st = L.blu_hip_tableau_row(self._h, int(r), int(bool(prepare_update)), None if sk is None else sk.ctypes.data or 8,
+                                       alpha.ctypes.data or 8, C.addressof(nz), self.ilhs.ctypes.data, self.lhs.ctypes.data or 8)
+        else:
+            st = L.blu_hip_tableau_row(self._h, int(r), int(bool(prepare_update)), None if sk is None else sk.ctypes.data or 8,
+                                       alpha.ctypes.data or 8, None, None, None)
+        if st == K.OK and want_solution:
+            self.nzlhs = int(nz.value)
+        elif st in (K.ERROR_DEVICE, K.ERROR_OUT_OF_MEMORY):
+            raise BluError(st, self.last_error())
+        return st, alpha
+
+    def price(self, y, skip=None):
+        """z[j] = A[:, j] . y for the resident matrix and a dense y of m entries; +0.0 where skip[j] != 0.  Errors raise."""
+        yy = np.ascontiguousarray(y, dtype=np.float64)
+        if yy.shape != (self.m,):
+            raise ValueError("price: y needs m = %d entries" % self.m)
+        z = np.zeros(getattr(self, "_ncol", 0))
+        sk = self._skip(skip, "price")
+        L = lib()
+        L.blu_hip_price.argtypes = [C.c_void_p] + [C.c_void_p] * 3
+        st = L.blu_hip_price(self._h, yy.ctypes.data or 8, None if sk is None else sk.ctypes.data or 8, z.ctypes.data or 8)
+        if st != K.OK:
+            raise BluError(st, self.last_error())
+        return z
+
+    def dbg_matrix_counts(self):
+        """The last price, or the last tableau_row behind its solve: (kernel launches, synchronizes, host-to-device
+        copies, bytes downloaded)."""
+        out = (C.c_int64 * 4)()
+        lib().blu_hip_dbg_matrix_counts.argtypes = [C.c_void_p, C.c_void_p]
+        lib().blu_hip_dbg_matrix_counts(self._h, out)
+        return tuple(int(x) for x in out)
+
+    def dbg_set_matrix_timing(self, on=True):
+        """Bracket the product kernel of tableau_row / price with two events (off by default)."""
+        lib().blu_hip_dbg_set_matrix_timing.argtypes = [C.c_void_p, C.c_int]
+        lib().blu_hip_dbg_set_matrix_timing(self._h, int(bool(on)))
+
+    def dbg_matrix_kernel_seconds(self):
+        """Device seconds of the product kernel in the last tableau_row / price made with dbg_set_matrix_timing."""
+        lib().blu_hip_dbg_matrix_kernel_seconds.restype = C.c_double
+        lib().blu_hip_dbg_matrix_kernel_seconds.argtypes = [C.c_void_p]
+        return float(lib().blu_hip_dbg_matrix_kernel_seconds(self._h))
 
     # --- test hooks (step-wise comparison with the oracle) -------------------------------------------
     def dbg_set_stop(self, n):

@@ -44,6 +44,7 @@ using pv_wave2::k_pivot_loop_wave2_r3;
 #include "k_chain.hip"
 #include "k_update.hip"
 #include "k_copy.hip"
+#include "k_matrix.hip"
 
 #define BLU_STOPPED_STATUS 100 /* debug stepping only */
 
@@ -126,6 +127,17 @@ struct blu_hip {
     long long *mv_rec;
     int64_t mv_chunk;            // debug: fixed chunk size (<= 0: the policy)
     int64_t mv_counts[4];        // last pass: chunks launched, candidates priced, candidates discarded behind a hit, hits
+    // blu_hip_set_matrix (blu_matrix.inc): the same buffers hold a VALIDATED A (every row index below m) while mx_set; the
+    // offsets once more on the host, y (m doubles), the products and the skip bytes (ncol each) on the device
+    bool mx_set;
+    int64_t mx_ncol;
+    std::vector<uint64_t> mx_hp; // ncol + 1 offsets, mx_hp[0] = 0
+    double *mx_y, *mx_out;
+    unsigned char *mx_skip;
+    int64_t mx_ycap, mx_colcap;  // entries mx_y / mx_out and mx_skip hold
+    int64_t mx_counts[4];        // last tableau_row (behind its solve) or price: launches, synchronizes, uploads, bytes downloaded
+    int mx_timing;               // debug: 1 = events around k_at_dot
+    double mx_kernel_s;          // ... its device seconds in the last call
     // blu_hip_copy_batch (blu_copy.inc) with this handle as the source: the staging block on the device (segment table,
     // destination pointers, the destinations' descriptors), kept for the next call, and the counts of the last call
     char *cp_stage;
@@ -203,6 +215,7 @@ static void free_upd(blu_hip *h);
 static void free_multi(blu_hip *h);
 static void free_sparse_multi(blu_hip *h);
 static void free_maxvolume(blu_hip *h);
+static void free_matrix(blu_hip *h);
 static void free_all(blu_hip *h)
 {
     DevLU &D = h->D;
@@ -222,6 +235,7 @@ static void free_all(blu_hip *h)
     free_multi(h);
     free_sparse_multi(h);
     free_maxvolume(h);
+    free_matrix(h);
     dfree(h->cp_stage);
     // everything else lives in the slab
     dfree(h->slab);
@@ -333,6 +347,14 @@ extern "C" blu_hip *blu_hip_new(int64_t m, int64_t b_nz, int device)
     h->mv_rec = nullptr;
     h->mv_chunk = 0;
     memset(h->mv_counts, 0, sizeof h->mv_counts);
+    h->mx_set = false;
+    h->mx_ncol = 0;
+    h->mx_y = h->mx_out = nullptr;
+    h->mx_skip = nullptr;
+    h->mx_ycap = h->mx_colcap = 0;
+    memset(h->mx_counts, 0, sizeof h->mx_counts);
+    h->mx_timing = 0;
+    h->mx_kernel_s = 0.0;
     h->cp_stage = nullptr;
     h->cp_stage_cap = 0;
     memset(h->cp_counts, 0, sizeof h->cp_counts);
@@ -984,6 +1006,9 @@ extern "C" int blu_hip_solve_dense(blu_hip *h, const double *rhs, double *lhs, c
 #include "blu_solve_sparse_batch.inc"
 #include "blu_solve_sparse_multi.inc"
 #include "blu_maxvolume.inc"
+static int solve_sparse_core(blu_hip *h, int64_t nzrhs, const uint64_t *irhs, const double *xrhs, int64_t *p_nzlhs, int64_t *ilhs, double *lhs,
+                             int tr);
+#include "blu_matrix.inc"
 #include "blu_copy.inc"
 
 // solve_sparse -- src/solve_sparse.rs:36-68, lu/solve_sparse.rs:11-360 (fresh factorization: nforrest == 0)
@@ -997,7 +1022,14 @@ extern "C" int blu_hip_solve_sparse(blu_hip *h, int64_t nzrhs, const uint64_t *i
     bool ok = nzrhs >= 0 && nzrhs <= h->m;
     for (int64_t n = 0; ok && n < nzrhs; n++) ok = irhs[n] < (uint64_t)h->m;
     if (!ok) return BLU_ERROR_INVALID_ARGUMENT;
-    *p_nzlhs = 0;
+    return solve_sparse_core(h, nzrhs, irhs, xrhs, p_nzlhs, ilhs, lhs, (trans == 't' || trans == 'T') ? 1 : 0);
+}
+// ... behind its checks; blu_hip_tableau_row (blu_matrix.inc) makes its transposed solve through this as well and passes
+// NULL p_nzlhs when the solution is to stay on the device: it is then not downloaded
+static int solve_sparse_core(blu_hip *h, int64_t nzrhs, const uint64_t *irhs, const double *xrhs, int64_t *p_nzlhs, int64_t *ilhs, double *lhs,
+                             int tr)
+{
+    if (p_nzlhs) *p_nzlhs = 0;
     if (h->m == 0) return BLU_OK;
     if (hipSetDevice(h->device) != hipSuccess) return BLU_ERROR_DEVICE;
     const size_t M = (size_t)h->m;
@@ -1010,7 +1042,6 @@ extern "C" int blu_hip_solve_sparse(blu_hip *h, int64_t nzrhs, const uint64_t *i
         if (!hip_ok(h, hipMemset(W.marked, 0, M * sizeof(int)), "hipMemset")) return BLU_ERROR_DEVICE;
         h->marker = 0;
     }
-    const int tr = (trans == 't' || trans == 'T') ? 1 : 0;
     if (h->nupdate > 0) return solve_sparse_updated(h, nzrhs, irhs, xrhs, p_nzlhs, ilhs, lhs, tr);
     if (tr) { // the transposed system ends with L': row-wise L
         const int st = ensure_lt(h);
@@ -1040,6 +1071,7 @@ extern "C" int blu_hip_solve_sparse(blu_hip *h, int64_t nzrhs, const uint64_t *i
     h->sp_l_flops += out[1];
     h->sp_u_flops += out[2];
     h->sp_branch = (int)out[3];
+    if (!p_nzlhs) return BLU_OK;
     if (nz > 0) {
         std::vector<int> il(nz);
         std::vector<double> xv(nz);

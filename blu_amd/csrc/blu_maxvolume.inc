@@ -94,6 +94,7 @@ extern "C" int blu_hip_maxvolume(blu_hip *h, int64_t ncol, const uint64_t *a_p, 
         return done(BLU_ERROR_INVALID_ARGUMENT);
     }
     if (hipSetDevice(h->device) != hipSuccess) return done(BLU_ERROR_DEVICE);
+    h->mx_set = false; // (blu_matrix.inc: the buffers of a set matrix get an A nobody validated)
     int st = mv_upload(h, ncol, a_p, a_i, a_x);
     if (st != BLU_OK) return done(st);
     st = mv_factorize(h, a_p, basis, nz);

@@ -364,6 +364,63 @@ int blu_hip_get_sparse_multi(blu_hip *h, int64_t *ilhs, double *xlhs);
 int blu_hip_maxvolume(blu_hip *h, int64_t ncol, const uint64_t *a_p, const uint64_t *a_i, const double *a_x,
                       int64_t *basis, int64_t *isbasic, double volumetol, int64_t *p_nupdate);
 
+/* The resident constraint matrix (no reference counterpart): the rectangular A of a simplex or branch-and-bound code is
+ * uploaded once and stays on the device, and the products of an iteration with it -- the pivot row
+ * alpha_r = A' (B^-T e_r), the pricing vector z = A' y -- are made there, next to the solves.
+ *
+ * blu_hip_set_matrix makes A resident and validated: ncol compressed columns, offsets relative to a_p[0] as in
+ * blu_hip_maxvolume; ncol < m and ncol == 0 are allowed; no valid factorization is needed.  Checked in this order before
+ * anything is touched, the previous matrix staying in place: NULL h or a_p BLU_ERROR_ARGUMENT_MISSING; ncol < 0 or above
+ * INT_MAX, a decreasing a_p, more than INT_MAX entries BLU_ERROR_INVALID_ARGUMENT; NULL a_i or a_x while A has entries
+ * BLU_ERROR_ARGUMENT_MISSING; any row index >= m BLU_ERROR_INVALID_ARGUMENT -- which is what lets the product kernel gather
+ * y[a_i[q]] without a bound test.  BLU_ERROR_OUT_OF_MEMORY or BLU_ERROR_DEVICE behind these checks leave no matrix set.
+ * The matrix lives in the buffers of blu_hip_maxvolume (20 bytes per entry) plus 8 m + 9 ncol bytes and a host copy of the
+ * offsets.  It is the handle's own, like the other pools: it survives blu_hip_factorize, blu_hip_update, the solves and
+ * blu_hip_copy_batch in either role, is not copied into a destination, and a destination keeps its own.
+ * blu_hip_maxvolume overwrites the buffers with a matrix whose row indices nobody checked: after it the four entries
+ * below answer BLU_ERROR_INVALID_CALL until the next blu_hip_set_matrix. */
+int blu_hip_set_matrix(blu_hip *h, int64_t ncol, const uint64_t *a_p, const uint64_t *a_i, const double *a_x);
+/* blu_hip_factorize of A[:, basis[0..m)] from the resident matrix with an m-sized upload: the status, factors,
+ * statistics and later behaviour, bit for bit, of blu_hip_factorize given the gathered columns.  NULL h or basis
+ * BLU_ERROR_ARGUMENT_MISSING; no matrix set BLU_ERROR_INVALID_CALL; a basis[i] outside [0, ncol)
+ * BLU_ERROR_INVALID_ARGUMENT with the handle untouched. */
+int blu_hip_factorize_columns(blu_hip *h, const int64_t *basis);
+/* The forward blu_hip_solve_for_update of column j of the resident matrix, nothing uploaded: the status, stored spike,
+ * solution, pattern order, bits and counters of blu_hip_solve_for_update(h, n_j, a_i_j, a_x_j, ..., 'N') with its checks in
+ * their order; BLU_ERROR_INVALID_CALL without a set matrix comes first among the call-state checks, and j outside
+ * [0, ncol) is BLU_ERROR_INVALID_ARGUMENT where that call refuses an index.  p_nzlhs, ilhs, lhs as there (all three or
+ * no solution). */
+int blu_hip_solve_for_update_column(blu_hip *h, int64_t j, int64_t *p_nzlhs, int64_t *ilhs, double *lhs);
+/* Row r of B^-1 A: alpha[j] = column j of A dotted with y = B^-T e_r, for all ncol columns.
+ * Step one is the transposed solve of e_r exactly as its single entry makes it -- prepare_update == 0:
+ * blu_hip_solve_sparse(h, 1, [r], [1.0], ..., 'T'); otherwise the transposed blu_hip_solve_for_update(h, ., [r], ., ..., 'T')
+ * with a solution, the leaving row of a dual simplex iteration, which stores the row eta -- with the same refusals in the
+ * same order, flop counters, marker and later behaviour of the handle.  If p_nzlhs, ilhs and lhs are all non-NULL they are
+ * filled as by that call (lhs all zero on entry); otherwise the solution is not downloaded.
+ * Step two stays on the device: y (m doubles the handle keeps) is cleared, k_scatter_lhs writes the compressed solution
+ * into it with the count read on the device, k_at_dot writes every alpha[j], and the ncol doubles are downloaded.
+ * skip may be NULL; otherwise skip[j] != 0 (a caller passes its isbasic) gives alpha[j] = +0.0 and column j is not read.
+ * The summation order is fixed (n = length of column j, t_q = a_x[q] * y[a_i[q]] rounded once, no fma, no term left out
+ * for being zero): n <= 64: s = +0.0, then s = s + t_q in storage order; n > 64: 64 partial sums p[l] = +0.0, then
+ * p[l] = p[l] + t_q for q - a_p[j] = l, l + 64, l + 128, ..., then for w = 32, 16, 8, 4, 2, 1: p[l] = p[l] + p[l + w] for
+ * l < w; the result is p[0].  It does not depend on ncol, on skip or on where the column falls in the launch.
+ * Additional refusals, in front of those of the solve: no matrix set BLU_ERROR_INVALID_CALL, then NULL alpha while
+ * ncol > 0 BLU_ERROR_ARGUMENT_MISSING.  A failure of step two (BLU_ERROR_DEVICE) leaves the handle as after the solve.
+ * Cost: what its single solve costs, plus one memset, two launches, one synchronize and one download of 8 ncol bytes, plus
+ * the upload of ncol bytes when skip is given; launches and synchronizes do not depend on ncol (ncol == 0: the solve
+ * alone). */
+int blu_hip_tableau_row(blu_hip *h, int64_t r, int prepare_update, const int64_t *skip, double *alpha, int64_t *p_nzlhs,
+                        int64_t *ilhs, double *lhs);
+/* z[j] = column j of the resident matrix dotted with the dense host vector y[0..m) (for the reduced costs d = c - A' y
+ * with y = blu_hip_solve_dense(c_B, 'T')): the kernel, the summation order and the skip of blu_hip_tableau_row.  Needs a
+ * set matrix (else BLU_ERROR_INVALID_CALL) but no factorization, and changes nothing observable on the handle.  NULL h,
+ * NULL y while m > 0 or NULL z while ncol > 0: BLU_ERROR_ARGUMENT_MISSING.  m == 0 gives every z[j] = +0.0.
+ * Cost: the upload of y, of skip when given, one launch, one synchronize, one download. */
+int blu_hip_price(blu_hip *h, const double *y, const int64_t *skip, double *z);
+/* The last blu_hip_price, or the part of the last blu_hip_tableau_row behind its solve: out[0] kernel launches,
+ * [1] synchronizes, [2] host-to-device copies, [3] bytes downloaded. */
+int blu_hip_dbg_matrix_counts(const blu_hip *h, int64_t out[4]);
+
 /* Copying a handle (no reference counterpart): the complete logical state of src goes into the n handles dst[0..n) of
  * the same m on the same device, so that many handles hold one factorization -- fresh or updated, a pending
  * blu_hip_solve_for_update included -- and the batch entries above can continue from it, each member its own way.

@@ -88,6 +88,14 @@ extern "C" {
         h: *mut BluHip, ncol: i64, a_p: *const u64, a_i: *const u64, a_x: *const f64, basis: *mut i64, isbasic: *mut i64, volumetol: f64,
         p_nupdate: *mut i64,
     ) -> c_int;
+    fn blu_hip_set_matrix(h: *mut BluHip, ncol: i64, a_p: *const u64, a_i: *const u64, a_x: *const f64) -> c_int;
+    fn blu_hip_factorize_columns(h: *mut BluHip, basis: *const i64) -> c_int;
+    fn blu_hip_solve_for_update_column(h: *mut BluHip, j: i64, p_nzlhs: *mut i64, ilhs: *mut i64, lhs: *mut f64) -> c_int;
+    fn blu_hip_tableau_row(
+        h: *mut BluHip, r: i64, prepare_update: c_int, skip: *const i64, alpha: *mut f64, p_nzlhs: *mut i64, ilhs: *mut i64, lhs: *mut f64,
+    ) -> c_int;
+    fn blu_hip_price(h: *mut BluHip, y: *const f64, skip: *const i64, z: *mut f64) -> c_int;
+    fn blu_hip_dbg_matrix_counts(h: *const BluHip, out: *mut i64) -> c_int;
     fn blu_hip_copy_batch(src: *mut BluHip, dst: *mut *mut BluHip, n: c_int, status: *mut c_int) -> c_int;
     fn blu_hip_clone(src: *mut BluHip) -> *mut BluHip;
     fn blu_hip_last_error(h: *const BluHip) -> *const c_char;
@@ -251,6 +259,8 @@ pub struct BLU {
     pub ilhs: Vec<LUInt>,
     /// Number of nonzeros in `lhs` (`blu.rs:16`).
     pub nzlhs: usize,
+    /// Columns of the resident constraint matrix (`set_matrix`); `None` while none is set through this object.
+    ncol: Option<usize>,
     /// Arrays are reallocated for max(realloc_factor, 1.0) times the required size (`blu.rs:18-20`, default 1.5).
     pub realloc_factor: f64,
 }
@@ -270,7 +280,7 @@ impl BLU {
         if h.is_null() {
             return None;
         }
-        Some(BLU { lu: LU { h }, m, device, lhs: vec![0.0; m], ilhs: vec![0; m], nzlhs: 0, realloc_factor: 1.5 })
+        Some(BLU { lu: LU { h }, m, device, lhs: vec![0.0; m], ilhs: vec![0; m], nzlhs: 0, ncol: None, realloc_factor: 1.5 })
     }
 
     /// A new object with the complete logical state of this one (`blu_hip_clone`: factors, update state, a pending
@@ -283,7 +293,7 @@ impl BLU {
             return None;
         }
         let m = self.m;
-        Some(BLU { lu: LU { h }, m, device: self.device, lhs: vec![0.0; m], ilhs: vec![0; m], nzlhs: 0, realloc_factor: self.realloc_factor })
+        Some(BLU { lu: LU { h }, m, device: self.device, lhs: vec![0.0; m], ilhs: vec![0; m], nzlhs: 0, ncol: None, realloc_factor: self.realloc_factor })
     }
 
     // the library grows its device storage itself (the loops of blu.rs:105-115, 277-283, 324-330): it gets the factor
@@ -424,6 +434,99 @@ impl BLU {
             *p = nupdate;
         }
         status_of(code)
+    }
+
+    /// Makes the rectangular `A` (`ncol` compressed columns, every row index below `m`) resident on the device
+    /// (`blu_hip_set_matrix`; no reference counterpart).  It stays until the next `set_matrix` or `maxvolume` call on this
+    /// object and is what `factorize_columns`, `solve_for_update_column`, `tableau_row` and `price` work on.
+    pub fn set_matrix(&mut self, ncol: usize, a_p: &[usize], a_i: &[usize], a_x: &[f64]) -> Result<(), Status> {
+        // the C side reads a_p[0..=ncol] and a_i / a_x[a_p[0]..a_p[ncol]): never hand it less
+        if a_p.len() != ncol + 1 || a_p.windows(2).any(|w| w[1] < w[0]) || a_p[ncol] > a_i.len() || a_p[ncol] > a_x.len() {
+            return Err(Status::ErrorInvalidArgument);
+        }
+        status_of(unsafe { blu_hip_set_matrix(self.lu.h, ncol as i64, a_p.as_ptr() as *const u64, a_i.as_ptr() as *const u64, a_x.as_ptr()) })?;
+        self.ncol = Some(ncol);
+        Ok(())
+    }
+
+    /// `factorize` of `A[:, basis]` from the resident matrix with an `m`-sized upload: the status, factors and statistics
+    /// of `factorize` given the gathered columns.
+    pub fn factorize_columns(&mut self, basis: &[LUInt]) -> Result<(), Status> {
+        if basis.len() != self.m {
+            return Err(Status::ErrorInvalidArgument);
+        }
+        self.push_realloc_factor();
+        status_of(unsafe { blu_hip_factorize_columns(self.lu.h, basis.as_ptr()) })
+    }
+
+    /// The forward `solve_for_update` of column `j` of the resident matrix, nothing uploaded; the solution is left in
+    /// `self.lhs` / `self.ilhs[..self.nzlhs]` when `want_solution`.
+    pub fn solve_for_update_column(&mut self, j: usize, want_solution: bool) -> Result<(), Status> {
+        self.clear_lhs();
+        let mut nz: i64 = 0;
+        let code = unsafe {
+            if want_solution {
+                blu_hip_solve_for_update_column(self.lu.h, j as i64, &mut nz, self.ilhs.as_mut_ptr(), self.lhs.as_mut_ptr())
+            } else {
+                blu_hip_solve_for_update_column(self.lu.h, j as i64, std::ptr::null_mut(), std::ptr::null_mut(), std::ptr::null_mut())
+            }
+        };
+        status_of(code)?;
+        if want_solution {
+            self.nzlhs = nz as usize;
+        }
+        Ok(())
+    }
+
+    /// Row `r` of `B^-1 A` for the resident matrix into `alpha[..ncol]`: the transposed solve of `e_r` -- `solve_sparse`, or
+    /// with `prepare_update` the transposed `solve_for_update`, the leaving row of a dual simplex iteration -- and the
+    /// products with every column on the device.  `skip[j] != 0` (a caller passes its `isbasic`) gives `alpha[j] = +0.0`.
+    /// With `want_solution` the solution of the solve is left in `self.lhs` / `self.ilhs[..self.nzlhs]`.
+    pub fn tableau_row(
+        &mut self, r: usize, prepare_update: bool, skip: Option<&[LUInt]>, alpha: &mut [f64], want_solution: bool,
+    ) -> Result<(), Status> {
+        let ncol = self.ncol.ok_or(Status::ErrorInvalidCall)?;
+        if alpha.len() < ncol || skip.map_or(false, |s| s.len() < ncol) {
+            return Err(Status::ErrorInvalidArgument);
+        }
+        let sk = skip.map_or(std::ptr::null(), |s| s.as_ptr());
+        let mut nz: i64 = 0;
+        let code = unsafe {
+            if want_solution {
+                self.clear_lhs();
+                blu_hip_tableau_row(
+                    self.lu.h, r as i64, prepare_update as c_int, sk, alpha.as_mut_ptr(), &mut nz, self.ilhs.as_mut_ptr(), self.lhs.as_mut_ptr(),
+                )
+            } else {
+                blu_hip_tableau_row(
+                    self.lu.h, r as i64, prepare_update as c_int, sk, alpha.as_mut_ptr(), std::ptr::null_mut(), std::ptr::null_mut(),
+                    std::ptr::null_mut(),
+                )
+            }
+        };
+        status_of(code)?;
+        if want_solution {
+            self.nzlhs = nz as usize;
+        }
+        Ok(())
+    }
+
+    /// `z[j]` = column `j` of the resident matrix dotted with the dense `y[..m]`, in the summation order of `tableau_row`;
+    /// needs no factorization.
+    pub fn price(&mut self, y: &[f64], skip: Option<&[LUInt]>, z: &mut [f64]) -> Result<(), Status> {
+        let ncol = self.ncol.ok_or(Status::ErrorInvalidCall)?;
+        if y.len() < self.m || z.len() < ncol || skip.map_or(false, |s| s.len() < ncol) {
+            return Err(Status::ErrorInvalidArgument);
+        }
+        status_of(unsafe { blu_hip_price(self.lu.h, y.as_ptr(), skip.map_or(std::ptr::null(), |s| s.as_ptr()), z.as_mut_ptr()) })
+    }
+
+    /// The last `price`, or the last `tableau_row` behind its solve: kernel launches, synchronizes, host-to-device
+    /// copies, bytes downloaded.
+    pub fn dbg_matrix_counts(&self) -> [i64; 4] {
+        let mut out = [0i64; 4];
+        unsafe { blu_hip_dbg_matrix_counts(self.lu.h, out.as_mut_ptr()) };
+        out
     }
 
     // lu_clear_lhs, blu.rs:380-395

@@ -33,6 +33,13 @@
 //               the clone still shares with the original is a use-after-free report from here on
 //   OP_COPY_INTO b_nz                                       a new handle with that size hint receives blu_hip_copy_batch from the
 //               current one (status BLU_OK expected), the original is freed and the tape continues on the copy
+//   OP_SET_MATRIX ncol a_p[ncol + 1] a_i[nnz] a_x[nnz] status   blu_hip_set_matrix with host arrays built here that end with their
+//               last entry (nnz = a_p[ncol], a_p[0] = 0); the records below use this ncol
+//   OP_FACT_COLUMNS basis[m] status                         blu_hip_factorize_columns
+//   OP_FORUPD_COLUMN j want status [nzlhs ilhs[nzlhs] lhs[m] if want and status == 0]      blu_hip_solve_for_update_column
+//   OP_TABLEAU_ROW r prepare_update has_skip skip[ncol if has_skip] want status [alpha[ncol] [nzlhs ilhs[nzlhs] lhs[m] if want]
+//               if status == 0]                             blu_hip_tableau_row into an alpha of exactly ncol entries
+//   OP_PRICE has_skip skip[ncol if has_skip] y[m] status [z[ncol] if status == 0]          blu_hip_price
 //   OP_END
 #include "../include/blu_hip.h"
 
@@ -51,12 +58,14 @@ extern "C" int blu_hip_dbg_set_sparse_multi_ws_bytes(blu_hip *h, int64_t bytes);
 extern "C" int blu_hip_dbg_set_maxvolume_chunk(blu_hip *h, int64_t n);
 
 enum { OP_END = 0, OP_NEW, OP_EXTRA, OP_PARAM, OP_FACT, OP_DENSE, OP_SPARSE, OP_FORUPD, OP_UPDATE, OP_STAT, OP_MULTI_WS, OP_DENSE_MULTI,
-       OP_SPARSE_MULTI_WS, OP_SPARSE_MULTI, OP_SPARSE_MULTI_GET, OP_MAXVOLUME, OP_MAXVOLUME_CHUNK, OP_CLONE, OP_COPY_INTO };
+       OP_SPARSE_MULTI_WS, OP_SPARSE_MULTI, OP_SPARSE_MULTI_GET, OP_MAXVOLUME, OP_MAXVOLUME_CHUNK, OP_CLONE, OP_COPY_INTO, OP_SET_MATRIX,
+       OP_FACT_COLUMNS, OP_FORUPD_COLUMN, OP_TABLEAU_ROW, OP_PRICE };
 static const int64_t TAPE_MAGIC = 0x3145504154554c42LL; // "BLUTAPE1"
 static const char *const OP_NAME[] = {"end", "new", "dbg_set_upd_extra", "set_param", "factorize", "solve_dense", "solve_sparse",
                                       "solve_for_update", "update", "get_stat", "dbg_set_multi_ws_bytes", "solve_dense_multi",
                                       "dbg_set_sparse_multi_ws_bytes", "solve_sparse_multi", "get_sparse_multi", "maxvolume",
-                                      "dbg_set_maxvolume_chunk", "clone", "copy_batch"};
+                                      "dbg_set_maxvolume_chunk", "clone", "copy_batch", "set_matrix", "factorize_columns",
+                                      "solve_for_update_column", "tableau_row", "price"};
 
 static std::vector<int64_t> tape;
 static size_t pos = 0;
@@ -139,9 +148,10 @@ int main(int argc, char **argv)
     pos = 1;
     blu_hip *h = nullptr;
     int64_t m = 0;
+    size_t ncol = 0; // of the last OP_SET_MATRIX
     for (;;) {
         op = word();
-        if (op < OP_END || op > OP_COPY_INTO) {
+        if (op < OP_END || op > OP_PRICE) {
             fprintf(stderr, "emu_replay: unknown record %lld after call %ld\n", (long long)op, ncall);
             return 2;
         }
@@ -323,6 +333,68 @@ int main(int argc, char **argv)
             same_int("status", status, BLU_OK);
             blu_hip_free(h);
             h = c;
+            break;
+        }
+        case OP_SET_MATRIX: {
+            ncol = (size_t)word();
+            const uint64_t *p = (const uint64_t *)take(ncol + 1);
+            const size_t nnz = (size_t)p[ncol];
+            // (copies that end with their last entry: an access behind them is an AddressSanitizer report)
+            std::vector<uint64_t> a_p(p, p + ncol + 1);
+            const uint64_t *ti = (const uint64_t *)take(nnz);
+            std::vector<uint64_t> a_i(ti, ti + nnz);
+            const double *tx = (const double *)take(nnz);
+            std::vector<double> a_x(tx, tx + nnz);
+            same_int("status", blu_hip_set_matrix(h, (int64_t)ncol, a_p.data(), nnz ? a_i.data() : nullptr, nnz ? a_x.data() : nullptr), word());
+            break;
+        }
+        case OP_FACT_COLUMNS: {
+            const int64_t *tb = take((size_t)m);
+            std::vector<int64_t> basis(tb, tb + m);
+            same_int("status", blu_hip_factorize_columns(h, basis.data()), word());
+            break;
+        }
+        case OP_FORUPD_COLUMN: {
+            const int64_t j = word();
+            const bool want = word() != 0;
+            std::vector<int64_t> ilhs((size_t)m, 0);
+            std::vector<double> lhs((size_t)m, 0.0);
+            int64_t nzlhs = 0;
+            const int st = want ? blu_hip_solve_for_update_column(h, j, &nzlhs, ilhs.data(), lhs.data())
+                                : blu_hip_solve_for_update_column(h, j, nullptr, nullptr, nullptr);
+            same_solution(st, m, nzlhs, ilhs, lhs, want);
+            break;
+        }
+        case OP_TABLEAU_ROW:
+        case OP_PRICE: {
+            const int64_t r = op == OP_TABLEAU_ROW ? word() : 0;
+            const int prepare = op == OP_TABLEAU_ROW ? (int)word() : 0;
+            const bool has_skip = word() != 0;
+            const int64_t *ts = take(has_skip ? ncol : 0);
+            std::vector<int64_t> skip(ts, ts + (has_skip ? ncol : 0));
+            std::vector<double> out(ncol, -7.25e300); // (exactly ncol entries)
+            if (op == OP_PRICE) {
+                const double *ty = (const double *)take((size_t)m);
+                std::vector<double> y(ty, ty + m);
+                const int st = blu_hip_price(h, y.data(), has_skip ? skip.data() : nullptr, out.data());
+                same_int("status", st, word());
+                if (st == BLU_OK) same_words("z", out.data(), take(ncol), ncol, true);
+                break;
+            }
+            const bool want = word() != 0;
+            std::vector<int64_t> ilhs((size_t)m, 0);
+            std::vector<double> lhs((size_t)m, 0.0);
+            int64_t nzlhs = 0;
+            const int st = blu_hip_tableau_row(h, r, prepare, has_skip ? skip.data() : nullptr, out.data(), want ? &nzlhs : nullptr,
+                                               want ? ilhs.data() : nullptr, want ? lhs.data() : nullptr);
+            same_int("status", st, word());
+            if (st != BLU_OK) break;
+            same_words("alpha", out.data(), take(ncol), ncol, true);
+            if (want) {
+                same_int("nzlhs", nzlhs, word());
+                same_words("ilhs", ilhs.data(), take((size_t)nzlhs), (size_t)nzlhs, false);
+                same_words("lhs", lhs.data(), take((size_t)m), (size_t)m, true);
+            }
             break;
         }
         case OP_STAT: {
