@@ -143,24 +143,18 @@ static void copy_host_state(const blu_hip *src, blu_hip *d, bool with_upd)
 
 extern "C" int blu_hip_copy_batch(blu_hip *src, blu_hip **dst, int n, int *status)
 {
-    auto fail_all = [&](int code) {
-        if (status)
-            for (int k = 0; k < n; k++) status[k] = code;
-        return code;
-    };
-    if (!src || !dst || n < 0) return fail_all(BLU_ERROR_ARGUMENT_MISSING);
+    if (!src || !dst || n < 0) return refuse_all(status, n, BLU_ERROR_ARGUMENT_MISSING);
     for (int k = 0; k < n; k++)
-        if (!dst[k]) return fail_all(BLU_ERROR_ARGUMENT_MISSING);
+        if (!dst[k]) return refuse_all(status, n, BLU_ERROR_ARGUMENT_MISSING);
     if (n == 0) return BLU_OK;
     {
-        std::vector<blu_hip *> sorted(dst, dst + n);
-        sorted.push_back(src); // (the source among the destinations counts as a handle twice)
-        std::sort(sorted.begin(), sorted.end());
-        if (std::adjacent_find(sorted.begin(), sorted.end()) != sorted.end()) return fail_all(BLU_ERROR_INVALID_ARGUMENT);
+        std::vector<blu_hip *> all(dst, dst + n);
+        all.push_back(src); // (the source among the destinations counts as a handle twice)
+        if (has_duplicate(std::move(all))) return refuse_all(status, n, BLU_ERROR_INVALID_ARGUMENT);
     }
     for (int k = 0; k < n; k++)
-        if (dst[k]->device != src->device || dst[k]->m != src->m) return fail_all(BLU_ERROR_INVALID_ARGUMENT);
-    if (hipSetDevice(src->device) != hipSuccess) return fail_all(BLU_ERROR_DEVICE);
+        if (dst[k]->device != src->device || dst[k]->m != src->m) return refuse_all(status, n, BLU_ERROR_INVALID_ARGUMENT);
+    if (hipSetDevice(src->device) != hipSuccess) return refuse_all(status, n, BLU_ERROR_DEVICE);
 
     int64_t counts[6] = {0, 0, 0, 0, 0, 0};
     const int64_t allocs0 = t_dalloc_calls;
@@ -250,9 +244,12 @@ extern "C" int blu_hip_copy_batch(blu_hip *src, blu_hip **dst, int n, int *statu
         }
         // the staging block: [segment table | destination pointers | DevLU per destination | FinishOut per destination]
         const size_t nseg = segs.size() + 2;
-        auto up = [](size_t x) { return (x + 255) & ~(size_t)255; };
-        const size_t oS = 0, oP = up(nseg * sizeof(CopySeg)), oD = oP + up(nseg * nl * sizeof(char *)), oO = oD + up(nl * sizeof(DevLU)),
-                     total = oO + up(nl * sizeof(FinishOut));
+        Stage blk;
+        const auto aS = blk.add<CopySeg>(nseg);
+        const auto aP = blk.add<char *>(nseg * nl);
+        const auto aD = blk.add<DevLU>(nl);
+        const auto aO = blk.add<FinishOut>(nl);
+        const size_t total = align_up(blk.bytes);
         if (total > src->cp_stage_cap) {
             dfree(src->cp_stage);
             src->cp_stage_cap = 0;
@@ -260,18 +257,16 @@ extern "C" int blu_hip_copy_batch(blu_hip *src, blu_hip **dst, int n, int *statu
             else ok = false;
         }
         if (ok) {
-            char *dev = src->cp_stage;
-            std::vector<char> stage(total, 0);
-            DevLU *sD = (DevLU *)(stage.data() + oD);
-            FinishOut *sO = (FinishOut *)(stage.data() + oO);
+            blk.dev = src->cp_stage; // (kept by the source for its next call)
+            blk.host_front(total);
             for (size_t k = 0; k < nl; k++) {
-                sD[k] = live[k]->D;
-                sO[k] = live[k]->O;
+                blk.h(aD)[k] = live[k]->D;
+                blk.h(aO)[k] = live[k]->O;
             }
-            add(dev + oD, sizeof(DevLU), (long long)sizeof(DevLU), [](blu_hip *d) { return d->dD; });
-            add(dev + oO, sizeof(FinishOut), (long long)sizeof(FinishOut), [](blu_hip *d) { return d->dO; });
-            CopySeg *sS = (CopySeg *)(stage.data() + oS);
-            char **sP = (char **)(stage.data() + oP);
+            add(blk.d(aD), sizeof(DevLU), (long long)sizeof(DevLU), [](blu_hip *d) { return d->dD; });
+            add(blk.d(aO), sizeof(FinishOut), (long long)sizeof(FinishOut), [](blu_hip *d) { return d->dO; });
+            CopySeg *sS = blk.h(aS);
+            char **sP = blk.h(aP);
             long long ntiles = 0;
             for (size_t s = 0; s < segs.size(); s++) {
                 const CopySegHost &g = segs[s];
@@ -297,11 +292,11 @@ extern "C" int blu_hip_copy_batch(blu_hip *src, blu_hip **dst, int n, int *statu
             group = std::max(1LL, std::min(group, 64LL));
             const long long groups = ((long long)nl + group - 1) / group;
             ok = tblocks * groups <= 0x7fffffffLL &&
-                 hip_ok(src, hipMemcpyAsync(dev, stage.data(), total, hipMemcpyHostToDevice, src->stream), "h2d copy tables");
+                 hip_ok(src, hipMemcpyAsync(blk.dev, blk.host.data(), total, hipMemcpyHostToDevice, src->stream), "h2d copy tables");
             counts[2]++;
             if (ok) {
-                hipLaunchKernelGGL(k_copy_fanout, dim3((unsigned)(tblocks * groups)), dim3(COPY_THREADS), 0, src->stream, (const CopySeg *)(dev + oS),
-                                   (int)segs.size(), (char *const *)(dev + oP), (int)nl, (int)group, (int)tblocks, ntiles);
+                hipLaunchKernelGGL(k_copy_fanout, dim3((unsigned)(tblocks * groups)), dim3(COPY_THREADS), 0, src->stream, blk.d(aS), (int)segs.size(),
+                                   blk.d(aP), (int)nl, (int)group, (int)tblocks, ntiles);
                 counts[0]++;
             }
             // (also after a failed upload: the host block must outlive the asynchronous copy)
@@ -322,13 +317,7 @@ extern "C" int blu_hip_copy_batch(blu_hip *src, blu_hip **dst, int n, int *statu
         if (result[k] == BLU_OK) copy_host_state(src, dst[k], with_upd);
     counts[3] = t_dalloc_calls - allocs0;
     memcpy(src->cp_counts, counts, sizeof counts);
-    int worst_err = 0, worst_pos = BLU_OK;
-    for (int k = 0; k < n; k++) {
-        if (status) status[k] = result[k];
-        if (result[k] < 0) worst_err = std::min(worst_err, result[k]);
-        else worst_pos = std::max(worst_pos, result[k]);
-    }
-    return worst_err < 0 ? worst_err : worst_pos;
+    return batch_return(result, status);
 }
 
 extern "C" blu_hip *blu_hip_clone(blu_hip *src)

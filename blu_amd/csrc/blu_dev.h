@@ -62,7 +62,7 @@ enum {
     ST_NEED_CW = 5,       // column arena exhausted (host compacts/grows, relaunches)
     ST_NEED_RW = 6,       // row arena exhausted
     ST_INVALID_ARG = 7,   // singletons.rs:119-201 checks failed
-    ST_ERROR = 8          // invariant violated (a reference assert! would have fired)
+    ST_ERROR = 8          // an invariant does not hold (a reference assert! would have fired)
 };
 
 struct Scalars {

@@ -70,7 +70,6 @@ struct BatchCtx {
         if (hipEventElapsedTime(&ms, pe[0], pe[1]) == hipSuccess) t_phase[which] += 1e-3 * ms;
     }
 };
-static const int kPending = -12345;
 
 // A single factorize runs its O(nnz) phases chip-wide: cooperative launch of `grid_blocks` workgroups on the one
 // matrix (GridScope, blu_dev.h).  Returns false if the launch was refused; the caller then takes the
@@ -614,31 +613,18 @@ static int factorize_batch_impl(blu_hip **hs, int n, const uint64_t *const *d_b_
 {
     if (n <= 0) return BLU_OK;
     blu_hip *h0 = hs[0];
-    // every early return reports itself in status[] too: a caller that looks at status[] alone must not
-    // read "OK" for handles that were never worked on
-    auto fail_all = [&](int code) {
-        if (status)
-            for (int k = 0; k < n; k++) status[k] = code;
-        return code;
-    };
-    for (int k = 0; k < n; k++)
-        if (!hs[k]) return fail_all(BLU_ERROR_INVALID_ARGUMENT);
-    // the factors every handle holds are invalid from here on, whatever happens next
+    // every early return reports itself in status[] too (refuse_all): a caller that looks at status[] alone must not
+    // read "OK" for handles that were never worked on.  No member is NULL: both callers have refused that.
+    // The factors every handle holds are invalid from here on, whatever happens next
     for (int k = 0; k < n; k++) reset_lu(hs[k]);
-    if (hipSetDevice(h0->device) != hipSuccess) return fail_all(BLU_ERROR_DEVICE);
+    if (hipSetDevice(h0->device) != hipSuccess) return refuse_all(status, n, BLU_ERROR_DEVICE);
+    if (const int st = batch_handles_refusal(hs, n); st != BLU_OK) return refuse_all(status, n, st); // (twice = two workgroups on one DevLU)
     for (int k = 0; k < n; k++)
-        if (hs[k]->device != h0->device) return fail_all(BLU_ERROR_INVALID_ARGUMENT);
-    if (n > 1) { // the same handle twice = two workgroups on one DevLU: rejected
-        std::vector<blu_hip *> sorted(hs, hs + n);
-        std::sort(sorted.begin(), sorted.end());
-        if (std::adjacent_find(sorted.begin(), sorted.end()) != sorted.end()) return fail_all(BLU_ERROR_INVALID_ARGUMENT);
-    }
-    for (int k = 0; k < n; k++)
-        if (b_i_len[k] > (uint64_t)kIntMax) return fail_all(BLU_ERROR_INVALID_ARGUMENT); // 32-bit device indices
+        if (b_i_len[k] > (uint64_t)kIntMax) return refuse_all(status, n, BLU_ERROR_INVALID_ARGUMENT); // 32-bit device indices
     BatchCtx B;
     if (!batch_init(B, hs, n)) {
         batch_release(B);
-        return fail_all(oom_or_device(h0));
+        return refuse_all(status, n, oom_or_device(h0));
     }
     for (int k = 0; k < n; k++) {
         blu_hip *h = hs[k];
@@ -661,17 +647,9 @@ static int factorize_batch_impl(blu_hip **hs, int n, const uint64_t *const *d_b_
     for (int k = 0; k < n; k++) any = any || B.result[k] == kPending;
     bool ok = true;
     if (any) ok = batch_factorize(B);
-    // return value: the most negative error if any handle failed, else the largest status
-    int worst_err = 0, worst_pos = BLU_OK;
-    for (int k = 0; k < n; k++) {
-        int r = B.result[k];
-        if (r == kPending) r = BLU_ERROR_DEVICE;
-        if (r < 0) reset_lu(hs[k]); // what the kernels counted before they refused B is not the reference's: it counts nothing (singletons.rs:119-259)
-        if (status) status[k] = r;
-        if (r < 0) worst_err = std::min(worst_err, r);
-        else worst_pos = std::max(worst_pos, r);
-    }
-    int worst = worst_err < 0 ? worst_err : worst_pos;
+    for (int k = 0; k < n; k++) // (kPending is negative too)
+        if (B.result[k] < 0) reset_lu(hs[k]); // what the kernels counted before they refused B is not the reference's: it counts nothing (singletons.rs:119-259)
+    int worst = batch_return(B.result, status);
     batch_release(B);
     if (!ok && worst >= 0) worst = BLU_ERROR_DEVICE;
     return worst;
@@ -753,24 +731,19 @@ extern "C" int blu_hip_factorize_batch(blu_hip **hs, int n, const uint64_t *cons
                                        const double *const *b_x, const uint64_t *b_i_len,
                                        int inputs_on_device, int *status)
 {
-    auto fail_all = [&](int code) {
-        if (status)
-            for (int k = 0; k < n; k++) status[k] = code;
-        return code;
-    };
-    if (!hs || n < 0 || (n > 0 && (!b_begin || !b_end || !b_i || !b_x || !b_i_len))) return fail_all(BLU_ERROR_ARGUMENT_MISSING);
+    if (!hs || n < 0 || (n > 0 && (!b_begin || !b_end || !b_i || !b_x || !b_i_len))) return refuse_all(status, n, BLU_ERROR_ARGUMENT_MISSING);
     if (n == 0) return BLU_OK;
     for (int k = 0; k < n; k++)
-        if (!hs[k]) return fail_all(BLU_ERROR_ARGUMENT_MISSING);
+        if (!hs[k]) return refuse_all(status, n, BLU_ERROR_ARGUMENT_MISSING);
     if (inputs_on_device) return factorize_batch_impl(hs, n, b_begin, b_end, b_i, b_x, b_i_len, status);
-    if (hipSetDevice(hs[0]->device) != hipSuccess) return fail_all(BLU_ERROR_DEVICE);
+    if (hipSetDevice(hs[0]->device) != hipSuccess) return refuse_all(status, n, BLU_ERROR_DEVICE);
     std::vector<const uint64_t *> pb(n), pe(n), pi(n);
     std::vector<const double *> px(n);
     for (int k = 0; k < n; k++) {
         const int up = upload_inputs(hs[k], b_begin[k], b_end[k], b_i[k], b_x[k], b_i_len[k]);
         if (up != BLU_OK) {
             for (int q = 0; q < n; q++) hs[q]->nupdate = -1; // nothing was factorized: no handle keeps stale factors
-            return fail_all(up);
+            return refuse_all(status, n, up);
         }
         pb[k] = (const uint64_t *)hs[k]->ob_begin;
         pe[k] = (const uint64_t *)hs[k]->ob_end;

@@ -830,6 +830,7 @@ static bool ensure_out(blu_hip *h, int64_t ln, int64_t un, bool upload = true)
 static int ensure_rows_ws(blu_hip *h, int64_t lnz, int64_t unz);
 static RowsWs rows_ws_of(blu_hip *h);
 static bool launch_rows(blu_hip *h, DevLU *dD, hipStream_t stream);
+#include "blu_batch.inc"
 #include "blu_driver.inc"
 
 // BLU::get_factors -- src/blu.rs:139, get_factors.rs:48-180

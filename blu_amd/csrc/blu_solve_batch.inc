@@ -4,7 +4,9 @@
 //                            (one workgroup per member; the same array ensure_lt builds, kept for later calls)
 //   k_solve_dense_batch      fresh factorizations (nupdate == 0): the sweeps of k_solve_dense
 //   k_solve_dense_upd_batch  updated factorizations (nupdate > 0): the body of k_solve_dense_upd
-// on one stream, one synchronize at the end.  The per-member descriptors are staged on the host and uploaded once.
+// on one stream, one synchronize at the end.  The per-member descriptors are staged on the host and uploaded once: a
+// Stage of blu_batch.inc, whose stage_alloc / stage_run are the round around the launches.  The refusals and the return
+// value are those of blu_batch.inc as well.
 
 // the row-wise L buffers alone -- what a forward dense solve reads -- for THIS factorization's L (ensure_lt allocates
 // them with the whole solve_sparse workspace; ensure_sparse_ws keeps what is allocated here)
@@ -26,30 +28,17 @@ static int ensure_lt_ws(blu_hip *h)
     return BLU_OK;
 }
 
-static size_t align_up(size_t x) { return (x + 255) & ~(size_t)255; }
-
 extern "C" int blu_hip_solve_dense_batch(blu_hip **hs, int n, const double *const *rhs, double *const *lhs, char trans,
                                          int inputs_on_device, int *status)
 {
     // refusals of the call as a whole: every status[k] carries the code, no handle is touched
-    auto fail_all = [&](int code) {
-        if (status)
-            for (int k = 0; k < n; k++) status[k] = code;
-        return code;
-    };
-    if (!hs || !rhs || !lhs || n < 0) return fail_all(BLU_ERROR_ARGUMENT_MISSING);
+    if (!hs || !rhs || !lhs || n < 0) return refuse_all(status, n, BLU_ERROR_ARGUMENT_MISSING);
     if (n == 0) return BLU_OK;
     for (int k = 0; k < n; k++)
-        if (!hs[k] || !rhs[k] || !lhs[k]) return fail_all(BLU_ERROR_ARGUMENT_MISSING);
+        if (!rhs[k] || !lhs[k]) return refuse_all(status, n, BLU_ERROR_ARGUMENT_MISSING);
+    if (const int st = batch_handles_refusal(hs, n); st != BLU_OK) return refuse_all(status, n, st);
     blu_hip *h0 = hs[0];
-    for (int k = 0; k < n; k++)
-        if (hs[k]->device != h0->device) return fail_all(BLU_ERROR_INVALID_ARGUMENT);
-    if (n > 1) { // the same handle twice = two waves on one work vector: rejected
-        std::vector<blu_hip *> sorted(hs, hs + n);
-        std::sort(sorted.begin(), sorted.end());
-        if (std::adjacent_find(sorted.begin(), sorted.end()) != sorted.end()) return fail_all(BLU_ERROR_INVALID_ARGUMENT);
-    }
-    if (hipSetDevice(h0->device) != hipSuccess) return fail_all(BLU_ERROR_DEVICE);
+    if (hipSetDevice(h0->device) != hipSuccess) return refuse_all(status, n, BLU_ERROR_DEVICE);
     const int tr = (trans == 't' || trans == 'T') ? 1 : 0;
 
     // per member: its kind, and what it needs before the launches
@@ -99,17 +88,19 @@ extern "C" int blu_hip_solve_dense_batch(blu_hip **hs, int n, const double *cons
     const int nb = (int)fresh_build.size(), nf = (int)order.size(), nu = (int)upd.size();
     order.insert(order.end(), upd.begin(), upd.end());
     const int na = nf + nu;
-    bool ok = true;
     if (na > 0) {
-        const size_t oD = 0, oO = align_up(oD + (size_t)na * sizeof(DevLU)), oM = align_up(oO + (size_t)nf * sizeof(FinishOut)),
-                     oW = align_up(oM + (size_t)na * sizeof(SolveMember)), oU = align_up(oW + (size_t)(nb + nu) * sizeof(SparseWs)),
-                     total = oU + (size_t)nu * sizeof(UpdWs);
-        std::vector<char> stage(total, 0);
-        DevLU *sD = (DevLU *)(stage.data() + oD);
-        FinishOut *sO = (FinishOut *)(stage.data() + oO);
-        SolveMember *sM = (SolveMember *)(stage.data() + oM);
-        SparseWs *sW = (SparseWs *)(stage.data() + oW);
-        UpdWs *sU = (UpdWs *)(stage.data() + oU);
+        Stage S;
+        const auto aD = S.add<DevLU>((size_t)na);
+        const auto aO = S.add<FinishOut>((size_t)nf);
+        const auto aM = S.add<SolveMember>((size_t)na);
+        const auto aW = S.add<SparseWs>((size_t)(nb + nu));
+        const auto aU = S.add<UpdWs>((size_t)nu);
+        S.host_front(S.bytes);
+        DevLU *sD = S.h(aD);
+        FinishOut *sO = S.h(aO);
+        SolveMember *sM = S.h(aM);
+        SparseWs *sW = S.h(aW);
+        UpdWs *sU = S.h(aU);
         for (int s = 0; s < na; s++) {
             const int k = order[s];
             blu_hip *h = hs[k];
@@ -129,33 +120,22 @@ extern "C" int blu_hip_solve_dense_batch(blu_hip **hs, int n, const double *cons
                 sU[s - nf] = h->uw;
             }
         }
-        char *dbuf = nullptr;
-        if (!hip_ok(h0, hipMalloc((void **)&dbuf, total), "hipMalloc")) {
-            (void)hipGetLastError();
-            for (int s = 0; s < na; s++) result[order[s]] = BLU_ERROR_OUT_OF_MEMORY;
+        auto launch = [&](hipStream_t stream) {
+            const DevLU *dD = S.d(aD);
+            const SolveMember *dM = S.d(aM);
+            const SparseWs *dW = S.d(aW);
+            if (nb > 0) hipLaunchKernelGGL(k_build_lt_batch, dim3(nb), dim3(1024), 0, stream, dD, dW);
+            if (nf > 0) hipLaunchKernelGGL(k_solve_dense_batch, dim3(nf), dim3(64), 0, stream, dD, S.d(aO), dM, tr);
+            if (nu > 0) hipLaunchKernelGGL(k_solve_dense_upd_batch, dim3(nu), dim3(64), 0, stream, dD + nf, dW + nb, S.d(aU), dM + nf, tr);
+        };
+        if (const int st = stage_alloc(h0, S); st != BLU_OK) {
+            for (int k : order) result[k] = st;
+        } else if (stage_run(h0, S, "h2d solve descriptors", "k_solve_dense_batch", launch, [] { return true; }) != BLU_OK) {
+            fail_members(h0, hs, order, result, BLU_ERROR_DEVICE);
         } else {
-            const DevLU *dD = (const DevLU *)(dbuf + oD);
-            const FinishOut *dO = (const FinishOut *)(dbuf + oO);
-            const SolveMember *dM = (const SolveMember *)(dbuf + oM);
-            const SparseWs *dW = (const SparseWs *)(dbuf + oW);
-            const UpdWs *dU = (const UpdWs *)(dbuf + oU);
-            hipStream_t stream = h0->stream;
-            ok = hip_ok(h0, hipMemcpyAsync(dbuf, stage.data(), total, hipMemcpyHostToDevice, stream), "h2d solve descriptors");
-            if (ok) {
-                if (nb > 0) hipLaunchKernelGGL(k_build_lt_batch, dim3(nb), dim3(1024), 0, stream, dD, dW);
-                if (nf > 0) hipLaunchKernelGGL(k_solve_dense_batch, dim3(nf), dim3(64), 0, stream, dD, dO, dM, tr);
-                if (nu > 0) hipLaunchKernelGGL(k_solve_dense_upd_batch, dim3(nu), dim3(64), 0, stream, dD + nf, dW + nb, dU, dM + nf, tr);
-                ok = hip_ok(h0, hipStreamSynchronize(stream), "k_solve_dense_batch");
-            }
-            (void)hipFree(dbuf);
             for (int s = 0; s < na; s++) {
                 const int k = order[s];
                 blu_hip *h = hs[k];
-                if (!ok) {
-                    if (h != h0) h->err = h0->err;
-                    result[k] = BLU_ERROR_DEVICE;
-                    continue;
-                }
                 if (s < nb) h->lt_for_nfact = h->nfactorize;
                 if (s >= nf) h->marker += 4;
                 result[k] = BLU_OK;
@@ -164,13 +144,5 @@ extern "C" int blu_hip_solve_dense_batch(blu_hip **hs, int n, const double *cons
             }
         }
     }
-    // return value: the most negative error if any member failed, else the largest status
-    int worst_err = 0, worst_pos = BLU_OK;
-    for (int k = 0; k < n; k++) {
-        const int r = result[k] == kPending ? BLU_ERROR_DEVICE : result[k];
-        if (status) status[k] = r;
-        if (r < 0) worst_err = std::min(worst_err, r);
-        else worst_pos = std::max(worst_pos, r);
-    }
-    return worst_err < 0 ? worst_err : worst_pos;
+    return batch_return(result, status);
 }

@@ -135,7 +135,7 @@ extern "C" int blu_hip_solve_sparse_multi(blu_hip *h, int64_t nrhs, const int64_
             return code;
         };
         int64_t filled = 0; // entries of the result buffer in use
-        std::vector<char> stage;
+        Stage S;
         std::vector<long long> out;
         for (int64_t c0 = 0; c0 < nrhs; c0 += C) {
             const int64_t nc = std::min<int64_t>(C, nrhs - c0);
@@ -143,13 +143,17 @@ extern "C" int blu_hip_solve_sparse_multi(blu_hip *h, int64_t nrhs, const int64_
             size_t tot = 0;
             for (int64_t s = 0; s < nc; s++)
                 if (result[(size_t)(c0 + s)] == BLU_OK) tot += (size_t)(rhs_ptr[c0 + s + 1] - rhs_ptr[c0 + s]);
-            const size_t oB = 0, oX = align_up(oB + (size_t)nc * sizeof(long long)), oC = align_up(oX + tot * sizeof(double)),
-                         oI = align_up(oC + (size_t)nc * sizeof(int)), total = oI + std::max<size_t>(tot, 1) * sizeof(int);
-            stage.assign(total, 0);
+            S.restart();
+            const auto aB = S.add<long long>((size_t)nc);
+            const auto aX = S.add<double>(tot);
+            const auto aC = S.add<int>((size_t)nc);
+            const auto aI = S.add<int>(std::max<size_t>(tot, 1));
+            const size_t total = S.bytes;
+            S.host_front(total);
             {
-                long long *beg = (long long *)(stage.data() + oB);
-                double *sx = (double *)(stage.data() + oX);
-                int *cnt = (int *)(stage.data() + oC), *si = (int *)(stage.data() + oI);
+                long long *beg = S.h(aB);
+                double *sx = S.h(aX);
+                int *cnt = S.h(aC), *si = S.h(aI);
                 size_t put = 0;
                 for (int64_t s = 0; s < nc; s++) {
                     const int64_t j = c0 + s, b = rhs_ptr[j], e = rhs_ptr[j + 1];
@@ -179,10 +183,10 @@ extern "C" int blu_hip_solve_sparse_multi(blu_hip *h, int64_t nrhs, const int64_
                     return fail(BLU_ERROR_DEVICE);
                 h->sm_marker = 0;
             }
-            if (!hip_ok(h, hipMemcpyAsync(h->sm_stage, stage.data(), total, hipMemcpyHostToDevice, stream), "h2d right-hand sides"))
+            S.dev = h->sm_stage; // (kept by the handle)
+            if (!hip_ok(h, hipMemcpyAsync(S.dev, S.host.data(), total, hipMemcpyHostToDevice, stream), "h2d right-hand sides"))
                 return fail(BLU_ERROR_DEVICE);
-            const MultiRhs R{(const long long *)(h->sm_stage + oB), (const int *)(h->sm_stage + oC), (const int *)(h->sm_stage + oI),
-                             (const double *)(h->sm_stage + oX)};
+            const MultiRhs R{S.d(aB), S.d(aC), S.d(aI), S.d(aX)};
             if (updated)
                 hipLaunchKernelGGL(k_solve_upd_multi, dim3((unsigned)nc), dim3(64), 0, stream, h->dD, h->sm_pool, h->sw, h->uw, R, tr, h->sm_marker,
                                    nz_sparse);
@@ -259,7 +263,7 @@ extern "C" int blu_hip_solve_sparse_multi(blu_hip *h, int64_t nrhs, const int64_
             h->ust.update_cost_numer += (double)r_flops;
         }
     }
-    return upd_batch_return(result, status);
+    return batch_return(result, status);
 }
 
 extern "C" int blu_hip_get_sparse_multi(blu_hip *h, int64_t *ilhs, double *xlhs)

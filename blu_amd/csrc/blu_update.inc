@@ -181,6 +181,17 @@ static int fetch_solution(blu_hip *h, int64_t *p_nzlhs, int64_t *ilhs, double *l
     return BLU_OK;
 }
 
+// UPD_ERROR of `who` ("update": k_update; "update path": the solves on updated factors, where mode 1 may already have
+// written an eta row or the spike): the factors may be half modified, so they are invalid from here on
+static int upd_invariant_violated(blu_hip *h, const char *who)
+{
+    char buf[128];
+    snprintf(buf, sizeof buf, "%s: invariant violated at kernel source line %d", who, h->ust.err_line);
+    h->err = buf;
+    h->nupdate = -1;
+    return BLU_ERROR_DEVICE;
+}
+
 // one launch of k_solve_upd with the storage-request loop around it; the right-hand side is on the device already
 // (h->d_irhs / h->d_xrhs after upload_rhs, or a column of the resident A of blu_hip_maxvolume)
 static int run_solve_upd(blu_hip *h, int mode, int want, int64_t nzrhs, int tr, const int *d_irhs, const double *d_xrhs)
@@ -195,13 +206,7 @@ static int run_solve_upd(blu_hip *h, int mode, int want, int64_t nzrhs, int tr, 
         h->marker += 4;
         if (!download_upd(h)) return BLU_ERROR_DEVICE;
         if (h->ust.status == UPD_OK) return BLU_OK;
-        if (h->ust.status == UPD_ERROR) {
-            char buf[128];
-            snprintf(buf, sizeof buf, "update path: invariant violated at kernel source line %d", h->ust.err_line);
-            h->err = buf;
-            h->nupdate = -1; // (mode 1 may already have written an eta row or the spike: the factors are invalid from here on)
-            return BLU_ERROR_DEVICE;
-        }
+        if (h->ust.status == UPD_ERROR) return upd_invariant_violated(h, "update path");
         st = grow_upd(h);
         if (st != BLU_OK) return st;
     }
@@ -257,13 +262,7 @@ extern "C" int blu_hip_update(blu_hip *h, double xtbl)
             return BLU_OK;
         }
         if (h->ust.status == UPD_SINGULAR) return BLU_ERROR_SINGULAR_UPDATE; // the old factorization is still valid
-        if (h->ust.status == UPD_ERROR) {
-            char buf[128];
-            snprintf(buf, sizeof buf, "update: invariant violated at kernel source line %d", h->ust.err_line);
-            h->err = buf;
-            h->nupdate = -1; // the factors may be half modified: invalid from here on
-            return BLU_ERROR_DEVICE;
-        }
+        if (h->ust.status == UPD_ERROR) return upd_invariant_violated(h, "update");
         st = grow_upd(h);
         if (st != BLU_OK) return st;
     }

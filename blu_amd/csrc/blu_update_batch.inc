@@ -10,66 +10,81 @@
 // synchronize and one download (every member's UpdState and counters): none of them per member.  Storage requests
 // (UPD_NEED_R / _UC / _W) are answered by grow_upd and those members alone are launched again, as blu_update.inc does
 // for one handle.
+// The pieces blu_hip_solve_sparse_batch (blu_solve_sparse_batch.inc) uses as well are here: run_upd_round,
+// build_lt_batch, take_upd_result, take_solve_counters and gather_solutions.  The refusals, the return value and the
+// staging block (Stage, stage_alloc / stage_run) are those of blu_batch.inc.
 
-// what a round needs on the device, for the members listed in `list` (indices into hs): descriptors, the UpdMember
-// records, the result slots, and the packed right-hand sides of the whole call (ir / xr, member k's at rhs_off[k])
+// what a round needs of the host, for the members listed in `list` (indices into hs) ...
 struct UpdRound {
     std::vector<int> list;
-    std::vector<UpdMember> mem; // mem[s] of list[s]; irhs / xrhs are filled in here
+    std::vector<UpdMember> mem; // mem[s] of list[s]; irhs / xrhs are filled in by the round
     std::vector<UpdResult> res; // OUT
+};
+// ... and the packed right-hand sides of the whole call: member k's begin at off[k] (indexed by member, not by list)
+struct UpdRhs {
+    std::vector<int> ir;
+    std::vector<double> xr;
+    std::vector<size_t> off;
 };
 
 template <class Launch>
-static int run_upd_round(blu_hip *h0, blu_hip **hs, UpdRound &R, const std::vector<int> &ir, const std::vector<double> &xr,
-                         const std::vector<size_t> &rhs_off, const char *what, Launch launch)
+static int run_upd_round(blu_hip *h0, blu_hip **hs, UpdRound &R, const UpdRhs &rhs, const char *what, Launch launch)
 {
     const size_t c = R.list.size();
-    const size_t oD = 0, oO = align_up(oD + c * sizeof(DevLU)), oW = align_up(oO + c * sizeof(FinishOut)), oU = align_up(oW + c * sizeof(SparseWs)),
-                 oM = align_up(oU + c * sizeof(UpdWs)), oX = align_up(oM + c * sizeof(UpdMember)), oI = align_up(oX + xr.size() * sizeof(double)),
-                 oR = align_up(oI + ir.size() * sizeof(int)), total = oR + c * sizeof(UpdResult);
-    char *dbuf = nullptr;
-    if (!hip_ok(h0, hipMalloc((void **)&dbuf, total), "hipMalloc")) {
-        (void)hipGetLastError();
-        return BLU_ERROR_OUT_OF_MEMORY;
-    }
-    std::vector<char> stage(oR, 0);
-    DevLU *sD = (DevLU *)(stage.data() + oD);
-    FinishOut *sO = (FinishOut *)(stage.data() + oO);
-    SparseWs *sW = (SparseWs *)(stage.data() + oW);
-    UpdWs *sU = (UpdWs *)(stage.data() + oU);
-    UpdMember *sM = (UpdMember *)(stage.data() + oM);
+    Stage S;
+    const auto aD = S.add<DevLU>(c);
+    const auto aO = S.add<FinishOut>(c);
+    const auto aW = S.add<SparseWs>(c);
+    const auto aU = S.add<UpdWs>(c);
+    const auto aM = S.add<UpdMember>(c);
+    const auto aX = S.add<double>(rhs.xr.size());
+    const auto aI = S.add<int>(rhs.ir.size());
+    const auto aR = S.add<UpdResult>(c); // (written by the kernels: not uploaded)
+    if (const int st = stage_alloc(h0, S); st != BLU_OK) return st;
+    S.host_front(aR.off);
     for (size_t s = 0; s < c; s++) {
         const int k = R.list[s];
         blu_hip *h = hs[k];
-        sD[s] = h->D;
-        sO[s] = h->O;
-        sW[s] = h->sw;
-        sU[s] = h->uw;
-        sM[s] = R.mem[s];
-        sM[s].irhs = ir.empty() ? nullptr : (const int *)(dbuf + oI) + rhs_off[(size_t)k];
-        sM[s].xrhs = xr.empty() ? nullptr : (const double *)(dbuf + oX) + rhs_off[(size_t)k];
+        S.h(aD)[s] = h->D;
+        S.h(aO)[s] = h->O;
+        S.h(aW)[s] = h->sw;
+        S.h(aU)[s] = h->uw;
+        UpdMember &M = S.h(aM)[s];
+        M = R.mem[s];
+        M.irhs = rhs.ir.empty() ? nullptr : S.d(aI) + rhs.off[(size_t)k];
+        M.xrhs = rhs.xr.empty() ? nullptr : S.d(aX) + rhs.off[(size_t)k];
     }
-    if (!xr.empty()) memcpy(stage.data() + oX, xr.data(), xr.size() * sizeof(double));
-    if (!ir.empty()) memcpy(stage.data() + oI, ir.data(), ir.size() * sizeof(int));
+    if (!rhs.xr.empty()) memcpy(S.h(aX), rhs.xr.data(), rhs.xr.size() * sizeof(double));
+    if (!rhs.ir.empty()) memcpy(S.h(aI), rhs.ir.data(), rhs.ir.size() * sizeof(int));
     R.res.assign(c, UpdResult());
-    hipStream_t stream = h0->stream;
-    bool ok = hip_ok(h0, hipMemcpyAsync(dbuf, stage.data(), oR, hipMemcpyHostToDevice, stream), "h2d update descriptors");
-    if (ok) {
-        launch((int)c, stream, (const DevLU *)(dbuf + oD), (const FinishOut *)(dbuf + oO), (const SparseWs *)(dbuf + oW), (const UpdWs *)(dbuf + oU),
-               (const UpdMember *)(dbuf + oM), (UpdResult *)(dbuf + oR));
-        ok = hip_ok(h0, hipStreamSynchronize(stream), what) &&
-             hip_ok(h0, hipMemcpy(R.res.data(), dbuf + oR, c * sizeof(UpdResult), hipMemcpyDeviceToHost), "d2h update states");
-    }
-    (void)hipFree(dbuf);
-    return ok ? BLU_OK : BLU_ERROR_DEVICE;
+    return stage_run(
+        h0, S, "h2d update descriptors", what,
+        [&](hipStream_t stream) { launch((int)c, stream, S.d(aD), S.d(aO), S.d(aW), S.d(aU), S.d(aM), S.d(aR)); },
+        [&] { return hip_ok(h0, hipMemcpy(R.res.data(), S.d(aR), c * sizeof(UpdResult), hipMemcpyDeviceToHost), "d2h update states"); });
+}
+// a round without right-hand sides
+template <class Launch> static int run_upd_round(blu_hip *h0, blu_hip **hs, UpdRound &R, const char *what, Launch launch)
+{
+    return run_upd_round(h0, hs, R, UpdRhs(), what, launch);
 }
 
-static void fail_members(blu_hip *h0, blu_hip **hs, const std::vector<int> &list, std::vector<int> &result, int code)
+// the row-wise L of the members in `list` (their buffers exist: ensure_lt_ws), one workgroup each in one launch.  If the
+// round fails its members get the code in result[]; the caller takes them off its own lists.
+static int build_lt_batch(blu_hip *h0, blu_hip **hs, const std::vector<int> &list, std::vector<int> &result)
 {
-    for (int k : list) {
-        if (hs[k] != h0) hs[k]->err = h0->err;
-        result[k] = code;
-    }
+    if (list.empty()) return BLU_OK;
+    UpdRound lt;
+    UpdMember M;
+    memset(&M, 0, sizeof M);
+    lt.list = list;
+    lt.mem.assign(list.size(), M);
+    const int st = run_upd_round(h0, hs, lt, "k_build_lt_batch",
+                                 [](int c, hipStream_t stream, const DevLU *dD, const FinishOut *, const SparseWs *dW, const UpdWs *,
+                                    const UpdMember *, UpdResult *) { hipLaunchKernelGGL(k_build_lt_batch, dim3(c), dim3(1024), 0, stream, dD, dW); });
+    if (st != BLU_OK) fail_members(h0, hs, list, result, st);
+    else
+        for (int k : list) hs[k]->lt_for_nfact = hs[k]->nfactorize;
+    return st;
 }
 
 // ensure_upd for the members in `list`: workspaces per member where they do not exist yet, then the row-wise L and the
@@ -77,8 +92,8 @@ static void fail_members(blu_hip *h0, blu_hip **hs, const std::vector<int> &list
 // leave the list.
 static void ensure_upd_batch(blu_hip *h0, blu_hip **hs, std::vector<int> &list, std::vector<int> &result)
 {
-    UpdRound lt, init;
-    std::vector<int> kept;
+    std::vector<int> lt;
+    UpdRound init;
     for (int k : list) {
         blu_hip *h = hs[k];
         int st = ensure_sparse_ws(h);
@@ -90,14 +105,10 @@ static void ensure_upd_batch(blu_hip *h0, blu_hip **hs, std::vector<int> &list, 
             result[k] = st;
             continue;
         }
-        kept.push_back(k);
-        UpdMember M;
-        memset(&M, 0, sizeof M);
-        if (need_lt) {
-            lt.list.push_back(k);
-            lt.mem.push_back(M);
-        }
+        if (need_lt) lt.push_back(k);
         if (need_init) { // the totals count over the life of the handle: LU::reset leaves them (lu.rs:329-359)
+            UpdMember M;
+            memset(&M, 0, sizeof M);
             M.carry[0] = h->ust.nsymperm_total;
             M.carry[1] = h->ust.nunsymperm_total;
             M.carry[2] = h->ust.nforrest_total;
@@ -105,51 +116,50 @@ static void ensure_upd_batch(blu_hip *h0, blu_hip **hs, std::vector<int> &list, 
             init.mem.push_back(M);
         }
     }
-    list.swap(kept);
-    const std::vector<int> no_i;
-    const std::vector<double> no_x;
-    const std::vector<size_t> no_off;
-    auto drop = [&](const std::vector<int> &failed, int code) {
-        fail_members(h0, hs, failed, result, code);
-        std::vector<int> rest;
-        for (int k : list)
-            if (result[k] == kPending) rest.push_back(k);
-        list.swap(rest);
-    };
-    if (!lt.list.empty()) {
-        const int st = run_upd_round(h0, hs, lt, no_i, no_x, no_off, "k_build_lt_batch",
-                                     [](int c, hipStream_t stream, const DevLU *dD, const FinishOut *, const SparseWs *dW, const UpdWs *,
-                                        const UpdMember *, UpdResult *) { hipLaunchKernelGGL(k_build_lt_batch, dim3(c), dim3(1024), 0, stream, dD, dW); });
-        if (st != BLU_OK) drop(lt.list, st);
-        else
-            for (int k : lt.list) hs[k]->lt_for_nfact = hs[k]->nfactorize;
-    }
-    std::vector<int> todo;
-    for (int k : init.list)
-        if (result[k] == kPending) todo.push_back(k);
-    if (todo.size() != init.list.size()) { // (a member that lost its row-wise L above does not go on)
-        UpdRound r2;
+    keep_pending(list, result);
+    if (build_lt_batch(h0, hs, lt, result) != BLU_OK) { // (a member that lost its row-wise L does not go on)
+        keep_pending(list, result);
+        UpdRound rest;
         for (size_t s = 0; s < init.list.size(); s++)
             if (result[init.list[s]] == kPending) {
-                r2.list.push_back(init.list[s]);
-                r2.mem.push_back(init.mem[s]);
+                rest.list.push_back(init.list[s]);
+                rest.mem.push_back(init.mem[s]);
             }
-        init = r2;
+        init = rest;
     }
-    if (!init.list.empty()) {
-        const int st = run_upd_round(h0, hs, init, no_i, no_x, no_off, "k_upd_init_batch",
-                                     [](int c, hipStream_t stream, const DevLU *dD, const FinishOut *dO, const SparseWs *, const UpdWs *dU,
-                                        const UpdMember *dM, UpdResult *dR) {
-                                         hipLaunchKernelGGL(k_upd_init_batch, dim3(c), dim3(1024), 0, stream, dD, dO, dU, dM, dR);
-                                     });
-        if (st != BLU_OK) drop(init.list, st);
-        else
-            for (size_t s = 0; s < init.list.size(); s++) {
-                blu_hip *h = hs[init.list[s]];
-                h->ust = init.res[s].st;
-                h->upd_for_nfact = h->nfactorize;
-            }
+    if (init.list.empty()) return;
+    const int st = run_upd_round(h0, hs, init, "k_upd_init_batch",
+                                 [](int c, hipStream_t stream, const DevLU *dD, const FinishOut *dO, const SparseWs *, const UpdWs *dU,
+                                    const UpdMember *dM, UpdResult *dR) {
+                                     hipLaunchKernelGGL(k_upd_init_batch, dim3(c), dim3(1024), 0, stream, dD, dO, dU, dM, dR);
+                                 });
+    if (st != BLU_OK) {
+        fail_members(h0, hs, init.list, result, st);
+        keep_pending(list, result);
+        return;
     }
+    for (size_t s = 0; s < init.list.size(); s++) {
+        blu_hip *h = hs[init.list[s]];
+        h->ust = init.res[s].st;
+        h->upd_for_nfact = h->nfactorize;
+    }
+}
+
+// what the kernel of the update path answered for member h (upd: k_update_batch, else k_solve_upd_batch): its status
+// when it is done, or kPending when it asked for storage, got it and is to be launched again
+static int take_upd_result(blu_hip *h, const UpdResult &res, bool upd)
+{
+    h->marker += 4;
+    h->ust = res.st;
+    const int us = h->ust.status;
+    if (us == UPD_OK) {
+        if (upd) h->nupdate++;
+        return BLU_OK;
+    }
+    if (upd && us == UPD_SINGULAR) return BLU_ERROR_SINGULAR_UPDATE; // the old factorization is still valid
+    if (us == UPD_ERROR) return upd_invariant_violated(h, upd ? "update" : "update path");
+    const int g = grow_upd(h);
+    return g == BLU_OK ? kPending : g;
 }
 
 // the storage-request loop over the members in `active` (run_solve_upd / the loop of blu_hip_update for one handle):
@@ -157,8 +167,7 @@ static void ensure_upd_batch(blu_hip *h0, blu_hip **hs, std::vector<int> &list, 
 // (mode 0: blu_solve_sparse_batch.inc).  mem[k] is what member k is handed (marker filled in here); on return
 // result[k] is set for every member and, for a solve that ended well, out[k] holds its counters.
 static void run_upd_batch(blu_hip *h0, blu_hip **hs, std::vector<int> active, std::vector<int> &result, int kind, int tr,
-                          const std::vector<UpdMember> &mem, const std::vector<int> &ir, const std::vector<double> &xr,
-                          const std::vector<size_t> &rhs_off, std::vector<UpdResult> &out)
+                          const std::vector<UpdMember> &mem, const UpdRhs &rhs, std::vector<UpdResult> &out)
 {
     const bool upd = kind == 1;
     const int mode = kind == 0 ? 1 : 0;
@@ -181,11 +190,11 @@ static void run_upd_batch(blu_hip *h0, blu_hip **hs, std::vector<int> active, st
         if (R.list.empty()) break;
         int st;
         if (upd)
-            st = run_upd_round(h0, hs, R, ir, xr, rhs_off, what,
+            st = run_upd_round(h0, hs, R, rhs, what,
                                [](int c, hipStream_t stream, const DevLU *dD, const FinishOut *, const SparseWs *dW, const UpdWs *dU,
                                   const UpdMember *dM, UpdResult *dR) { hipLaunchKernelGGL(k_update_batch, dim3(c), dim3(64), 0, stream, dD, dW, dU, dM, dR); });
         else
-            st = run_upd_round(h0, hs, R, ir, xr, rhs_off, what,
+            st = run_upd_round(h0, hs, R, rhs, what,
                                [mode, tr](int c, hipStream_t stream, const DevLU *dD, const FinishOut *, const SparseWs *dW, const UpdWs *dU,
                                     const UpdMember *dM, UpdResult *dR) {
                                    hipLaunchKernelGGL(k_solve_upd_batch, dim3(c), dim3(64), 0, stream, dD, dW, dU, dM, dR, mode, tr);
@@ -196,27 +205,9 @@ static void run_upd_batch(blu_hip *h0, blu_hip **hs, std::vector<int> active, st
         }
         for (size_t s = 0; s < R.list.size(); s++) {
             const int k = R.list[s];
-            blu_hip *h = hs[k];
-            h->marker += 4;
-            h->ust = R.res[s].st;
-            const int us = h->ust.status;
-            if (us == UPD_OK) {
-                if (upd) h->nupdate++;
-                out[(size_t)k] = R.res[s];
-                result[k] = BLU_OK;
-            } else if (upd && us == UPD_SINGULAR) {
-                result[k] = BLU_ERROR_SINGULAR_UPDATE; // the old factorization is still valid
-            } else if (us == UPD_ERROR) {
-                char buf[128];
-                snprintf(buf, sizeof buf, "%s: invariant violated at kernel source line %d", upd ? "update" : "update path", h->ust.err_line);
-                h->err = buf;
-                h->nupdate = -1; // the factors may be half modified: invalid from here on
-                result[k] = BLU_ERROR_DEVICE;
-            } else {
-                const int g = grow_upd(h);
-                if (g == BLU_OK) active.push_back(k);
-                else result[k] = g;
-            }
+            result[k] = take_upd_result(hs[k], R.res[s], upd);
+            if (result[k] == BLU_OK) out[(size_t)k] = R.res[s];
+            else if (result[k] == kPending) active.push_back(k);
         }
     }
     for (int k : active) {
@@ -225,54 +216,67 @@ static void run_upd_batch(blu_hip *h0, blu_hip **hs, std::vector<int> active, st
     }
 }
 
-// the refusals the batch entries of the update path and blu_hip_solve_sparse_batch share; BLU_OK = go on
-static int upd_batch_refusal(blu_hip **hs, int n)
+// the counters of a sparse solve that ended well, as fetch_solution takes them
+static void take_solve_counters(blu_hip *h, const UpdResult &r)
 {
-    for (int k = 0; k < n; k++)
-        if (!hs[k]) return BLU_ERROR_ARGUMENT_MISSING;
-    for (int k = 0; k < n; k++)
-        if (hs[k]->device != hs[0]->device) return BLU_ERROR_INVALID_ARGUMENT;
-    if (n > 1) { // the same handle twice = two waves on one factorization: rejected
-        std::vector<blu_hip *> sorted(hs, hs + n);
-        std::sort(sorted.begin(), sorted.end());
-        if (std::adjacent_find(sorted.begin(), sorted.end()) != sorted.end()) return BLU_ERROR_INVALID_ARGUMENT;
-    }
-    return BLU_OK;
+    h->sp_l_flops += r.out[1];
+    h->sp_u_flops += r.out[2];
+    h->sp_branch = (int)r.out[3];
 }
 
-// return value: the most negative error if any member failed, else the largest status
-static int upd_batch_return(const std::vector<int> &result, int *status)
+// The compressed solutions of the members in `got` -- member got[s] has off[s + 1] - off[s] entries -- gathered on the
+// device, one copy down, and unpacked into the caller's arrays.  Nothing happens when there is no entry at all; if the
+// round fails, the members of `got` fail.
+static void gather_solutions(blu_hip *h0, blu_hip **hs, const std::vector<int> &got, const std::vector<long long> &off,
+                             std::vector<int> &result, int64_t *nzlhs, int64_t *const *ilhs, double *const *lhs)
 {
-    int worst_err = 0, worst_pos = BLU_OK;
-    for (size_t k = 0; k < result.size(); k++) {
-        const int r = result[k] == kPending ? BLU_ERROR_DEVICE : result[k];
-        if (status) status[k] = r;
-        if (r < 0) worst_err = std::min(worst_err, r);
-        else worst_pos = std::max(worst_pos, r);
+    const size_t c = got.size(), tot = (size_t)off.back();
+    if (tot == 0) return;
+    Stage S;
+    const auto aW = S.add<SparseWs>(c);
+    const auto aF = S.add<long long>(c + 1);
+    const auto aV = S.add<double>(tot); // (values and patterns: written by the kernel, not uploaded)
+    const auto aI = S.add<int>(tot);
+    S.host_front(aV.off);
+    for (size_t s = 0; s < c; s++) S.h(aW)[s] = hs[got[s]]->sw;
+    memcpy(S.h(aF), off.data(), (c + 1) * sizeof(long long));
+    std::vector<char> down(S.bytes - aV.off);
+    int st = stage_alloc(h0, S);
+    if (st == BLU_OK)
+        st = stage_run(
+            h0, S, "h2d gather descriptors", "k_gather_lhs_batch",
+            [&](hipStream_t stream) {
+                hipLaunchKernelGGL(k_gather_lhs_batch, dim3((unsigned)c), dim3(256), 0, stream, S.d(aW), S.d(aF), S.d(aI), S.d(aV));
+            },
+            [&] { return hip_ok(h0, hipMemcpy(down.data(), S.d(aV), down.size(), hipMemcpyDeviceToHost), "d2h solutions"); });
+    if (st != BLU_OK) {
+        fail_members(h0, hs, got, result, st);
+        return;
     }
-    return worst_err < 0 ? worst_err : worst_pos;
+    const double *xv = (const double *)down.data();
+    const int *il = (const int *)(down.data() + (aI.off - aV.off));
+    for (size_t s = 0; s < c; s++) {
+        const int k = got[s];
+        for (long long p = off[s]; p < off[s + 1]; p++) { // pattern in the reference's order, values into the caller's (all-zero) lhs
+            ilhs[k][p - off[s]] = il[p];
+            lhs[k][il[p]] = xv[p];
+        }
+        nzlhs[k] = off[s + 1] - off[s];
+    }
 }
 
 extern "C" int blu_hip_solve_for_update_batch(blu_hip **hs, int n, const int64_t *nzrhs, const uint64_t *const *irhs, const double *const *xrhs,
                                               int64_t *nzlhs, int64_t *const *ilhs, double *const *lhs, char trans, int *status)
 {
     // refusals of the call as a whole: every status[k] carries the code, no handle is touched
-    auto fail_all = [&](int code) {
-        if (status)
-            for (int k = 0; k < n; k++) status[k] = code;
-        return code;
-    };
     const int tr = (trans == 't' || trans == 'T') ? 1 : 0;
-    if (!hs || !irhs || n < 0 || (!tr && (!xrhs || !nzrhs))) return fail_all(BLU_ERROR_ARGUMENT_MISSING);
+    if (!hs || !irhs || n < 0 || (!tr && (!xrhs || !nzrhs))) return refuse_all(status, n, BLU_ERROR_ARGUMENT_MISSING);
     if (n == 0) return BLU_OK;
     for (int k = 0; k < n; k++)
-        if (!irhs[k] || (!tr && !xrhs[k])) return fail_all(BLU_ERROR_ARGUMENT_MISSING);
-    {
-        const int st = upd_batch_refusal(hs, n);
-        if (st != BLU_OK) return fail_all(st);
-    }
+        if (!irhs[k] || (!tr && !xrhs[k])) return refuse_all(status, n, BLU_ERROR_ARGUMENT_MISSING);
+    if (const int st = batch_handles_refusal(hs, n); st != BLU_OK) return refuse_all(status, n, st);
     blu_hip *h0 = hs[0];
-    if (hipSetDevice(h0->device) != hipSuccess) return fail_all(BLU_ERROR_DEVICE);
+    if (hipSetDevice(h0->device) != hipSuccess) return refuse_all(status, n, BLU_ERROR_DEVICE);
     const bool want_any = nzlhs && ilhs && lhs;
 
     // per member, in the order of blu_hip_solve_for_update
@@ -284,9 +288,8 @@ extern "C" int blu_hip_solve_for_update_batch(blu_hip **hs, int n, const int64_t
     }
     ensure_upd_batch(h0, hs, active, result);
     std::vector<UpdMember> mem((size_t)n);
-    std::vector<size_t> rhs_off((size_t)n, 0);
-    std::vector<int> ir;
-    std::vector<double> xr;
+    UpdRhs rhs;
+    rhs.off.assign((size_t)n, 0);
     {
         std::vector<int> kept;
         for (int k : active) {
@@ -313,86 +316,38 @@ extern "C" int blu_hip_solve_for_update_batch(blu_hip **hs, int n, const int64_t
             if (M.want_solution) nzlhs[k] = 0;
             M.nrhs = (int)nz;
             M.nz_sparse = (int)(h->sparse_thres * (double)h->m);
-            rhs_off[(size_t)k] = ir.size();
-            for (int64_t q = 0; q < nz; q++) ir.push_back((int)irhs[k][q]);
-            if (!tr) xr.insert(xr.end(), xrhs[k], xrhs[k] + nz);
+            rhs.off[(size_t)k] = rhs.ir.size();
+            for (int64_t q = 0; q < nz; q++) rhs.ir.push_back((int)irhs[k][q]);
+            if (!tr) rhs.xr.insert(rhs.xr.end(), xrhs[k], xrhs[k] + nz);
             kept.push_back(k);
         }
         active.swap(kept);
     }
-    if (tr) xr.assign(ir.size(), 0.0); // (never read: one layout for both systems)
+    if (tr) rhs.xr.assign(rhs.ir.size(), 0.0); // (never read: one layout for both systems)
     std::vector<UpdResult> out((size_t)n);
-    run_upd_batch(h0, hs, active, result, 0, tr, mem, ir, xr, rhs_off, out);
+    run_upd_batch(h0, hs, active, result, 0, tr, mem, rhs, out);
 
-    // the counters as fetch_solution takes them, then the compressed solutions: gathered on the device, one copy down
+    // the counters, then the compressed solutions of every member that asked for one (the empty ones included)
     std::vector<int> got;
     std::vector<long long> off(1, 0);
     for (int k : active) {
         if (result[k] != BLU_OK) continue;
-        blu_hip *h = hs[k];
-        h->sp_l_flops += out[(size_t)k].out[1];
-        h->sp_u_flops += out[(size_t)k].out[2];
-        h->sp_branch = (int)out[(size_t)k].out[3];
+        take_solve_counters(hs[k], out[(size_t)k]);
         if (!mem[(size_t)k].want_solution) continue;
         got.push_back(k);
         off.push_back(off.back() + out[(size_t)k].out[0]);
     }
-    const size_t tot = (size_t)off.back();
-    if (tot > 0) {
-        const size_t c = got.size();
-        const size_t oW = 0, oF = align_up(oW + c * sizeof(SparseWs)), oV = align_up(oF + (c + 1) * sizeof(long long)),
-                     oI = align_up(oV + tot * sizeof(double)), total = oI + tot * sizeof(int);
-        std::vector<char> stage(oV, 0), down(total - oV);
-        for (size_t s = 0; s < c; s++) ((SparseWs *)(stage.data() + oW))[s] = hs[got[s]]->sw;
-        memcpy(stage.data() + oF, off.data(), (c + 1) * sizeof(long long));
-        char *dbuf = nullptr;
-        int st = BLU_OK;
-        if (!hip_ok(h0, hipMalloc((void **)&dbuf, total), "hipMalloc")) {
-            (void)hipGetLastError();
-            st = BLU_ERROR_OUT_OF_MEMORY;
-        } else {
-            bool ok = hip_ok(h0, hipMemcpyAsync(dbuf, stage.data(), oV, hipMemcpyHostToDevice, h0->stream), "h2d gather descriptors");
-            if (ok) {
-                hipLaunchKernelGGL(k_gather_lhs_batch, dim3((unsigned)c), dim3(256), 0, h0->stream, (const SparseWs *)(dbuf + oW),
-                                   (const long long *)(dbuf + oF), (int *)(dbuf + oI), (double *)(dbuf + oV));
-                ok = hip_ok(h0, hipStreamSynchronize(h0->stream), "k_gather_lhs_batch") &&
-                     hip_ok(h0, hipMemcpy(down.data(), dbuf + oV, total - oV, hipMemcpyDeviceToHost), "d2h solutions");
-            }
-            (void)hipFree(dbuf);
-            if (!ok) st = BLU_ERROR_DEVICE;
-        }
-        if (st != BLU_OK) fail_members(h0, hs, got, result, st);
-        else {
-            const double *xv = (const double *)down.data();
-            const int *il = (const int *)(down.data() + (oI - oV));
-            for (size_t s = 0; s < c; s++) {
-                const int k = got[s];
-                for (long long p = off[s]; p < off[s + 1]; p++) { // pattern in the reference's order, values into the caller's (all-zero) lhs
-                    ilhs[k][p - off[s]] = il[p];
-                    lhs[k][il[p]] = xv[p];
-                }
-                nzlhs[k] = off[s + 1] - off[s];
-            }
-        }
-    }
-    return upd_batch_return(result, status);
+    gather_solutions(h0, hs, got, off, result, nzlhs, ilhs, lhs);
+    return batch_return(result, status);
 }
 
 extern "C" int blu_hip_update_batch(blu_hip **hs, int n, const double *xtbl, int *status)
 {
-    auto fail_all = [&](int code) {
-        if (status)
-            for (int k = 0; k < n; k++) status[k] = code;
-        return code;
-    };
-    if (!hs || !xtbl || n < 0) return fail_all(BLU_ERROR_ARGUMENT_MISSING);
+    if (!hs || !xtbl || n < 0) return refuse_all(status, n, BLU_ERROR_ARGUMENT_MISSING);
     if (n == 0) return BLU_OK;
-    {
-        const int st = upd_batch_refusal(hs, n);
-        if (st != BLU_OK) return fail_all(st);
-    }
+    if (const int st = batch_handles_refusal(hs, n); st != BLU_OK) return refuse_all(status, n, st);
     blu_hip *h0 = hs[0];
-    if (hipSetDevice(h0->device) != hipSuccess) return fail_all(BLU_ERROR_DEVICE);
+    if (hipSetDevice(h0->device) != hipSuccess) return refuse_all(status, n, BLU_ERROR_DEVICE);
     std::vector<int> result(n, kPending), active;
     std::vector<UpdMember> mem((size_t)n);
     for (int k = 0; k < n; k++) {
@@ -405,10 +360,7 @@ extern "C" int blu_hip_update_batch(blu_hip **hs, int n, const double *xtbl, int
         mem[(size_t)k].xtbl = xtbl[k];
         active.push_back(k);
     }
-    const std::vector<int> no_i;
-    const std::vector<double> no_x;
-    const std::vector<size_t> no_off;
     std::vector<UpdResult> out((size_t)n);
-    run_upd_batch(h0, hs, active, result, 1, 0, mem, no_i, no_x, no_off, out);
-    return upd_batch_return(result, status);
+    run_upd_batch(h0, hs, active, result, 1, 0, mem, UpdRhs(), out);
+    return batch_return(result, status);
 }
