@@ -365,6 +365,124 @@ def copy_batch(src, dsts):
     return out
 
 
+def share_matrix(src, dsts):
+    """Every handle of `dsts` (same m, same device) holds the resident matrix `src` holds afterwards
+    (blu_hip_share_matrix): one copy of A on the device for all of them, no device copy and no launch.  A destination that
+    has a matrix lets go of it first.  Returns the per-member statuses.  A refused call raises BluError, as does
+    ERROR_DEVICE or ERROR_OUT_OF_MEMORY of a member."""
+    n = len(dsts)
+    L = lib()
+    L.blu_hip_share_matrix.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p]
+    N = max(n, 1)
+    hs = (C.c_void_p * N)(*[h._h for h in dsts])
+    st = (C.c_int * N)()
+    rc = L.blu_hip_share_matrix(src._h, hs, n, st)
+    if rc in (K.ERROR_ARGUMENT_MISSING, K.ERROR_INVALID_ARGUMENT, K.ERROR_INVALID_CALL):  # (only a refusal of the whole call)
+        raise BluError(rc, "share_matrix refused")
+    out = [int(s) for s in st][:n]
+    for h, s in zip(dsts, out):
+        if s in (K.ERROR_DEVICE, K.ERROR_OUT_OF_MEMORY):
+            raise BluError(s, h.last_error() or src.last_error())
+        h._ncol = getattr(src, "_ncol", 0)
+    return out
+
+
+def _matrix_batch_refused(rc, handles, what):
+    """ERROR_INVALID_ARGUMENT is also a member's status (a row out of range): it is a refusal of the whole call for a
+    handle twice, two devices, or members that do not hold one matrix -- then every member carries it."""
+    if rc == K.ERROR_ARGUMENT_MISSING:
+        raise BluError(rc, what + " refused")
+    _refused(rc, handles, what)
+    L = lib()
+    L.blu_hip_dbg_matrix_id.restype = C.c_void_p
+    L.blu_hip_dbg_matrix_id.argtypes = [C.c_void_p]
+    if rc == K.ERROR_INVALID_ARGUMENT and len({L.blu_hip_dbg_matrix_id(h._h) for h in handles} - {None}) > 1:
+        raise BluError(rc, what + " refused: the handles do not hold one matrix")
+
+
+def _skip_pointers(handles, skips, what):
+    """(array of pointers or None, the arrays kept alive)"""
+    n = len(handles)
+    if skips is None:
+        return None, []
+    if len(skips) != n:
+        raise ValueError(what + ": one skip (or None) per handle")
+    keep = [h._skip(s, what) for h, s in zip(handles, skips)]
+    ps = (C.c_void_p * max(n, 1))()
+    for k, sk in enumerate(keep):
+        ps[k] = None if sk is None else sk.ctypes.data or 8
+    return ps, keep
+
+
+def tableau_row_batch(handles, rows, prepare_update=False, skips=None, want_solution=False):
+    """BLU.tableau_row(rows[k], prepare_update, skips[k]) for len(handles) handles that hold one matrix (share_matrix) in
+    one call: per member the status, the bits of alpha, the solution and the statistics of the single call.  skips may be
+    None, and so may any skips[k].  With want_solution each handle's previous solution is cleared and the new one left in
+    h.lhs / h.ilhs[0..h.nzlhs).  Returns (statuses, alphas).  A refused call raises BluError, as does ERROR_DEVICE or
+    ERROR_OUT_OF_MEMORY of a member; the other codes are only reported in the member's status."""
+    n = len(handles)
+    if len(rows) != n:
+        raise ValueError("tableau_row_batch: one row per handle")
+    L = lib()
+    L.blu_hip_tableau_row_batch.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_int] + [C.c_void_p] * 6
+    N = max(n, 1)
+    hs = (C.c_void_p * N)(*[h._h for h in handles])
+    rr = (C.c_int64 * N)(*[int(r) for r in rows])
+    alphas = [np.zeros(getattr(h, "_ncol", 0)) for h in handles]
+    pa, pil, pl = (C.c_void_p * N)(), (C.c_void_p * N)(), (C.c_void_p * N)()
+    ps, keep = _skip_pointers(handles, skips, "tableau_row_batch")
+    for k, h in enumerate(handles):
+        pa[k] = alphas[k].ctypes.data or 8
+        if want_solution:
+            h._clear_lhs()
+            pil[k], pl[k] = h.ilhs.ctypes.data, h.lhs.ctypes.data or 8
+    nzl = (C.c_int64 * N)()
+    st = (C.c_int * N)()
+    rc = L.blu_hip_tableau_row_batch(hs, n, rr, int(bool(prepare_update)), ps, pa, nzl if want_solution else None,
+                                     pil if want_solution else None, pl if want_solution else None, st)
+    _matrix_batch_refused(rc, handles, "tableau_row_batch")
+    out = [int(s) for s in st][:n]
+    for k, (h, s) in enumerate(zip(handles, out)):
+        if s in (K.ERROR_DEVICE, K.ERROR_OUT_OF_MEMORY):
+            raise BluError(s, h.last_error() or handles[0].last_error())
+        if s == K.OK and want_solution:
+            h.nzlhs = int(nzl[k])
+    del keep
+    return out, alphas
+
+
+def price_batch(handles, ys, skips=None):
+    """BLU.price(ys[k], skips[k]) for len(handles) handles that hold one matrix in one call: (statuses, zs), z[k] with
+    the bits of the single call.  A member without a matrix gets ERROR_INVALID_CALL.  A refused call raises BluError, as
+    does ERROR_DEVICE or ERROR_OUT_OF_MEMORY of a member."""
+    n = len(handles)
+    if len(ys) != n:
+        raise ValueError("price_batch: one y per handle")
+    yy = [np.ascontiguousarray(y, dtype=np.float64) for y in ys]
+    for h, y in zip(handles, yy):
+        if y.shape != (h.m,):
+            raise ValueError("price_batch: y needs m = %d entries" % h.m)
+    L = lib()
+    L.blu_hip_price_batch.argtypes = [C.c_void_p, C.c_int] + [C.c_void_p] * 4
+    N = max(n, 1)
+    hs = (C.c_void_p * N)(*[h._h for h in handles])
+    zs = [np.zeros(getattr(h, "_ncol", 0)) for h in handles]
+    py, pz = (C.c_void_p * N)(), (C.c_void_p * N)()
+    ps, keep = _skip_pointers(handles, skips, "price_batch")
+    for k in range(n):
+        py[k], pz[k] = yy[k].ctypes.data or 8, zs[k].ctypes.data or 8
+    st = (C.c_int * N)()
+    rc = L.blu_hip_price_batch(hs, n, py, ps, pz, st)
+    out = [int(s) for s in st][:n]
+    if rc in (K.ERROR_ARGUMENT_MISSING, K.ERROR_INVALID_ARGUMENT):  # (codes only a refusal of the whole call returns)
+        raise BluError(rc, "price_batch refused")
+    for h, s in zip(handles, out):
+        if s in (K.ERROR_DEVICE, K.ERROR_OUT_OF_MEMORY):
+            raise BluError(s, h.last_error() or handles[0].last_error())
+    del keep
+    return out, zs
+
+
 class BLU:
     """`struct BLU` (src/blu.rs:9-20) backed by the HIP implementation."""
 
@@ -749,6 +867,17 @@ class BLU:
         lib().blu_hip_dbg_matrix_counts.argtypes = [C.c_void_p, C.c_void_p]
         lib().blu_hip_dbg_matrix_counts(self._h, out)
         return tuple(int(x) for x in out)
+
+    def dbg_matrix_holders(self):
+        """Handles that hold this handle's matrix, itself included (share_matrix); 0 when none is set."""
+        lib().blu_hip_dbg_matrix_holders.argtypes = [C.c_void_p]
+        return int(lib().blu_hip_dbg_matrix_holders(self._h))
+
+    def dbg_set_matrix_batch_bytes(self, n):
+        """Byte limit of the device block of tableau_row_batch / price_batch for this handle's matrix (n < 0: the
+        default), so that small calls take several chunks; results do not depend on it."""
+        lib().blu_hip_dbg_set_matrix_batch_bytes.argtypes = [C.c_void_p, C.c_int64]
+        return int(lib().blu_hip_dbg_set_matrix_batch_bytes(self._h, int(n)))
 
     def dbg_set_matrix_timing(self, on=True):
         """Bracket the product kernel of tableau_row / price with two events (off by default)."""

@@ -1,6 +1,6 @@
 // blu_batch.inc -- what the batched entries of the C ABI share on the host (included by blu_hip.hip ahead of
 // blu_driver.inc): blu_hip_factorize_batch, _solve_dense_batch, _solve_for_update_batch, _update_batch,
-// _solve_sparse_batch, _solve_sparse_multi and _copy_batch.
+// _solve_sparse_batch, _solve_sparse_multi, _copy_batch, _share_matrix, _tableau_row_batch and _price_batch.
 //   * a call is refused as a whole (refuse_all: every status[k] carries the code) or answers per member: result[k]
 //     starts as kPending, and batch_return writes status[] and picks the return value;
 //   * the handle list of a call (batch_handles_refusal), the members a failed launch takes with it (fail_members) and

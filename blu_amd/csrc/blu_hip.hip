@@ -48,6 +48,21 @@ using pv_wave2::k_pivot_loop_wave2_r3;
 
 #define BLU_STOPPED_STATUS 100 /* debug stepping only */
 
+// One resident matrix held by several handles (blu_hip_share_matrix, blu_matrix.inc): the device arrays of A and the
+// host offsets exist once, here, and the holders' mv_* / mx_hp fields alias them.  The last holder that detaches frees
+// them.  The block also keeps the device block of the batched products (blu_matrix_batch.inc).
+struct MatShare {
+    int refs;
+    long long *ap;
+    unsigned long long *ai64;
+    int *ai;
+    double *ax;
+    std::vector<uint64_t> hp;
+    char *bt;         // y tiles, products, masks and scatter descriptors of one chunk of a batched call
+    size_t bt_cap;
+    int64_t bt_limit; // debug: byte limit of bt (< 0: the default)
+};
+
 struct blu_hip {
     int device;
     int64_t m, b_nz_hint;
@@ -131,7 +146,10 @@ struct blu_hip {
     // offsets once more on the host, y (m doubles), the products and the skip bytes (ncol each) on the device
     bool mx_set;
     int64_t mx_ncol;
-    std::vector<uint64_t> mx_hp; // ncol + 1 offsets, mx_hp[0] = 0
+    const uint64_t *mx_hp;       // ncol + 1 offsets, mx_hp[0] = 0: mx_hp_own's, or the shared block's
+    std::vector<uint64_t> mx_hp_own;
+    MatShare *mx_share;          // blu_hip_share_matrix: the block that owns mv_ap / mv_ai64 / mv_ai / mv_ax and the offsets while
+                                 // the handle's fields alias them (NULL: the handle owns them itself)
     double *mx_y, *mx_out;
     unsigned char *mx_skip;
     int64_t mx_ycap, mx_colcap;  // entries mx_y / mx_out and mx_skip hold
@@ -349,6 +367,8 @@ extern "C" blu_hip *blu_hip_new(int64_t m, int64_t b_nz, int device)
     memset(h->mv_counts, 0, sizeof h->mv_counts);
     h->mx_set = false;
     h->mx_ncol = 0;
+    h->mx_hp = nullptr;
+    h->mx_share = nullptr;
     h->mx_y = h->mx_out = nullptr;
     h->mx_skip = nullptr;
     h->mx_ycap = h->mx_colcap = 0;
@@ -1005,6 +1025,7 @@ extern "C" int blu_hip_solve_dense(blu_hip *h, const double *rhs, double *lhs, c
 #include "blu_solve_multi.inc"
 #include "blu_update_batch.inc"
 #include "blu_solve_sparse_batch.inc"
+#include "blu_matrix_batch.inc"
 #include "blu_solve_sparse_multi.inc"
 #include "blu_maxvolume.inc"
 static int solve_sparse_core(blu_hip *h, int64_t nzrhs, const uint64_t *irhs, const double *xrhs, int64_t *p_nzlhs, int64_t *ilhs, double *lhs,

@@ -2,6 +2,9 @@
 // the device with a public lifetime, and the products of an iteration with it.
 //   blu_hip_set_matrix                uploads A into the buffers of blu_hip_maxvolume (mv_upload) after validating it;
 //                                     every row index is below m from then on, which k_at_dot relies on
+//   blu_hip_share_matrix              the matrix of one handle held by many: the arrays of A and the host offsets move into a
+//                                     reference-counted block (MatShare) that the holders' mv_* / mx_hp fields alias; mx_detach
+//                                     (blu_maxvolume.inc) is how a holder leaves.  The batched products: blu_matrix_batch.inc
 //   blu_hip_factorize_columns         blu_hip_factorize of A[:, basis] with an m-sized upload (mv_factorize)
 //   blu_hip_solve_for_update_column   the forward blu_hip_solve_for_update of column j, nothing uploaded
 //   blu_hip_tableau_row               row r of B^-1 A: the transposed solve of e_r as its single entry makes it, then on the
@@ -14,6 +17,25 @@ static void free_matrix(blu_hip *h)
     dfree(h->mx_y); dfree(h->mx_out); dfree(h->mx_skip);
     h->mx_ycap = h->mx_colcap = 0;
     h->mx_set = false;
+}
+
+// what a handle with a matrix of ncol columns has besides A: y (m doubles), the products and the skip bytes (ncol each)
+static int mx_work_buffers(blu_hip *h, int64_t ncol)
+{
+    const size_t M = (size_t)h->m, N = (size_t)ncol;
+    if ((int64_t)M > h->mx_ycap) {
+        dfree(h->mx_y);
+        h->mx_ycap = 0;
+        if (!dalloc(h, &h->mx_y, M)) return BLU_ERROR_OUT_OF_MEMORY;
+        h->mx_ycap = (int64_t)M;
+    }
+    if ((int64_t)N > h->mx_colcap) {
+        dfree(h->mx_out); dfree(h->mx_skip);
+        h->mx_colcap = 0;
+        if (!dalloc(h, &h->mx_out, N) || !dalloc(h, &h->mx_skip, N)) return BLU_ERROR_OUT_OF_MEMORY;
+        h->mx_colcap = (int64_t)N;
+    }
+    return BLU_OK;
 }
 
 extern "C" int blu_hip_set_matrix(blu_hip *h, int64_t ncol, const uint64_t *a_p, const uint64_t *a_i, const double *a_x)
@@ -30,27 +52,91 @@ extern "C" int blu_hip_set_matrix(blu_hip *h, int64_t ncol, const uint64_t *a_p,
         if (a_i[base + q] >= (uint64_t)h->m) return BLU_ERROR_INVALID_ARGUMENT;
     if (hipSetDevice(h->device) != hipSuccess) return BLU_ERROR_DEVICE;
     h->mx_set = false; // (from here on the buffers change)
-    const size_t M = (size_t)h->m, N = (size_t)ncol;
-    if ((int64_t)M > h->mx_ycap) {
-        dfree(h->mx_y);
-        h->mx_ycap = 0;
-        if (!dalloc(h, &h->mx_y, M)) return BLU_ERROR_OUT_OF_MEMORY;
-        h->mx_ycap = (int64_t)M;
-    }
-    if ((int64_t)N > h->mx_colcap) {
-        dfree(h->mx_out); dfree(h->mx_skip);
-        h->mx_colcap = 0;
-        if (!dalloc(h, &h->mx_out, N) || !dalloc(h, &h->mx_skip, N)) return BLU_ERROR_OUT_OF_MEMORY;
-        h->mx_colcap = (int64_t)N;
-    }
-    const int st = mv_upload(h, ncol, a_p, a_i, a_x);
+    const size_t N = (size_t)ncol;
+    int st = mx_work_buffers(h, ncol);
     if (st != BLU_OK) return st;
-    h->mx_hp.resize(N + 1);
-    for (size_t j = 0; j <= N; j++) h->mx_hp[j] = a_p[j] - base;
+    st = mv_upload(h, ncol, a_p, a_i, a_x);
+    if (st != BLU_OK) return st;
+    h->mx_hp_own.resize(N + 1);
+    for (size_t j = 0; j <= N; j++) h->mx_hp_own[j] = a_p[j] - base;
+    h->mx_hp = h->mx_hp_own.data();
     h->mx_ncol = ncol;
     h->mx_set = true;
     return BLU_OK;
 }
+
+// the block that owns h's set matrix; a handle that owns its arrays itself hands them over and becomes the first holder
+static MatShare *mx_share_block(blu_hip *h)
+{
+    if (h->mx_share) return h->mx_share;
+    MatShare *S = new MatShare();
+    S->refs = 1;
+    S->ap = h->mv_ap;
+    S->ai64 = h->mv_ai64;
+    S->ai = h->mv_ai;
+    S->ax = h->mv_ax;
+    S->hp = std::move(h->mx_hp_own);
+    S->bt = nullptr;
+    S->bt_cap = 0;
+    S->bt_limit = -1;
+    h->mx_hp = S->hp.data();
+    h->mx_share = S;
+    return S;
+}
+
+// Every dst[k] holds the matrix src holds afterwards: no device copy of A and no launch.  A destination lets go of the
+// matrix it has (its own arrays are freed, a shared one is detached), gets y / products / skip bytes of its own, and
+// aliases the block.
+extern "C" int blu_hip_share_matrix(blu_hip *src, blu_hip **dst, int n, int *status)
+{
+    // refusals of the call as a whole: every status[k] carries the code, nothing is touched
+    if (!src || !dst || n < 0) return refuse_all(status, n, BLU_ERROR_ARGUMENT_MISSING);
+    for (int k = 0; k < n; k++)
+        if (!dst[k]) return refuse_all(status, n, BLU_ERROR_ARGUMENT_MISSING);
+    if (!src->mx_set) return refuse_all(status, n, BLU_ERROR_INVALID_CALL);
+    if (n == 0) return BLU_OK;
+    for (int k = 0; k < n; k++)
+        if (dst[k] == src || dst[k]->device != src->device || dst[k]->m != src->m) return refuse_all(status, n, BLU_ERROR_INVALID_ARGUMENT);
+    if (has_duplicate(std::vector<blu_hip *>(dst, dst + n))) return refuse_all(status, n, BLU_ERROR_INVALID_ARGUMENT);
+    if (hipSetDevice(src->device) != hipSuccess) return refuse_all(status, n, BLU_ERROR_DEVICE);
+
+    MatShare *S = mx_share_block(src);
+    std::vector<int> result(n, kPending);
+    for (int k = 0; k < n; k++) {
+        blu_hip *h = dst[k];
+        if (h->mx_share == S && h->mx_set) { // (holds it already)
+            result[k] = BLU_OK;
+            continue;
+        }
+        h->mx_set = false;
+        mx_detach(h);
+        dfree(h->mv_ap); dfree(h->mv_ai64); dfree(h->mv_ai); dfree(h->mv_ax);
+        h->mv_pcap = h->mv_nzcap = 0;
+        std::vector<uint64_t>().swap(h->mx_hp_own);
+        h->mx_hp = nullptr;
+        result[k] = mx_work_buffers(h, src->mx_ncol);
+        if (result[k] != BLU_OK) continue; // (left without a matrix)
+        S->refs++;
+        h->mx_share = S;
+        h->mv_ap = S->ap;
+        h->mv_ai64 = S->ai64;
+        h->mv_ai = S->ai;
+        h->mv_ax = S->ax;
+        h->mx_hp = S->hp.data();
+        h->mx_ncol = src->mx_ncol;
+        h->mx_set = true;
+    }
+    return batch_return(result, status);
+}
+
+// handles that hold h's matrix, h included; 0 when none is set
+extern "C" int blu_hip_dbg_matrix_holders(const blu_hip *h)
+{
+    if (!h || !h->mx_set) return 0;
+    return h->mx_share ? h->mx_share->refs : 1;
+}
+// what tells one resident matrix from another (the device pointer of its offsets); NULL when none is set
+extern "C" const void *blu_hip_dbg_matrix_id(const blu_hip *h) { return h && h->mx_set ? (const void *)h->mv_ap : nullptr; }
 
 extern "C" int blu_hip_factorize_columns(blu_hip *h, const int64_t *basis)
 {
@@ -59,7 +145,7 @@ extern "C" int blu_hip_factorize_columns(blu_hip *h, const int64_t *basis)
     for (int64_t i = 0; i < h->m; i++)
         if (basis[i] < 0 || basis[i] >= h->mx_ncol) return BLU_ERROR_INVALID_ARGUMENT;
     if (hipSetDevice(h->device) != hipSuccess) return BLU_ERROR_DEVICE;
-    return mv_factorize(h, h->mx_hp.data(), basis, h->mx_hp[(size_t)h->mx_ncol]);
+    return mv_factorize(h, h->mx_hp, basis, h->mx_hp[(size_t)h->mx_ncol]);
 }
 
 // the checks of the forward blu_hip_solve_for_update in their order (blu_update.inc), the column taken from the resident A

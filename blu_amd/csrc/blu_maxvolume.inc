@@ -11,8 +11,30 @@
 // the transposed solve, the update and the refactorization rule as in the loop; what the chunk priced behind it is thrown
 // away and priced again against the new factors.  A is uploaded once per pass.
 
+// The handle lets go of a matrix it holds with others (blu_hip_share_matrix): the reference is dropped, the last holder
+// frees the arrays, and the handle goes on as one that never had buffers.  The two places that write or free the arrays
+// of A -- mv_upload and free_maxvolume -- come through here first.
+static void mx_detach(blu_hip *h)
+{
+    MatShare *S = h->mx_share;
+    if (!S) return;
+    if (--S->refs == 0) {
+        dfree(S->ap); dfree(S->ai64); dfree(S->ai); dfree(S->ax); dfree(S->bt);
+        delete S;
+    }
+    h->mx_share = nullptr;
+    h->mv_ap = nullptr;
+    h->mv_ai64 = nullptr;
+    h->mv_ai = nullptr;
+    h->mv_ax = nullptr;
+    h->mv_pcap = h->mv_nzcap = 0;
+    h->mx_hp = nullptr;
+    h->mx_set = false;
+}
+
 static void free_maxvolume(blu_hip *h)
 {
+    mx_detach(h);
     dfree(h->mv_ap); dfree(h->mv_ai64); dfree(h->mv_ai); dfree(h->mv_ax); dfree(h->mv_cols); dfree(h->mv_rec);
     h->mv_pcap = h->mv_nzcap = h->mv_colscap = 0;
 }
@@ -22,6 +44,7 @@ static int mv_upload(blu_hip *h, int64_t ncol, const uint64_t *a_p, const uint64
 {
     const uint64_t base = a_p[0];
     const size_t np = (size_t)ncol + 1, nz = (size_t)(a_p[ncol] - base);
+    mx_detach(h);
     if ((int64_t)np > h->mv_pcap) {
         dfree(h->mv_ap);
         h->mv_pcap = 0;

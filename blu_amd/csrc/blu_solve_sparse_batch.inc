@@ -11,24 +11,17 @@
 // request -- unexpected for mode 0 -- is grown and launched again through run_upd_batch, as blu_hip_solve_sparse does
 // for one handle.  Refusals and the return value: blu_batch.inc.
 
-extern "C" int blu_hip_solve_sparse_batch(blu_hip **hs, int n, const int64_t *nzrhs, const uint64_t *const *irhs, const double *const *xrhs,
-                                          int64_t *nzlhs, int64_t *const *ilhs, double *const *lhs, char trans, int *status)
+// The call behind its refusals as a whole, for the members whose result[k] is still kPending: the checks of each member in
+// the order of blu_hip_solve_sparse, the round, the counters.  gather[k] != 0: member k's compressed solution is downloaded
+// into nzlhs[k] / ilhs[k] / lhs[k]; every member's stays in its sw.ilhs / sw.xval / sw.out[0] on the device, which is what
+// blu_hip_tableau_row_batch (blu_matrix_batch.inc) goes on from.
+static void solve_sparse_batch_core(blu_hip *h0, blu_hip **hs, int n, const int64_t *nzrhs, const uint64_t *const *irhs, const double *const *xrhs,
+                                    int64_t *nzlhs, int64_t *const *ilhs, double *const *lhs, int tr, const std::vector<char> &gather,
+                                    std::vector<int> &result)
 {
-    // refusals of the call as a whole: every status[k] carries the code, no handle is touched
-    if (!hs || !nzrhs || !nzlhs || !ilhs || !lhs || n < 0) return refuse_all(status, n, BLU_ERROR_ARGUMENT_MISSING);
-    if (n == 0) return BLU_OK;
+    std::vector<int> fresh, updated, lt;
     for (int k = 0; k < n; k++) {
-        if (!hs[k] || !ilhs[k] || !lhs[k]) return refuse_all(status, n, BLU_ERROR_ARGUMENT_MISSING);
-        if (nzrhs[k] > 0 && (!irhs || !xrhs || !irhs[k] || !xrhs[k])) return refuse_all(status, n, BLU_ERROR_ARGUMENT_MISSING);
-    }
-    if (const int st = batch_handles_refusal(hs, n); st != BLU_OK) return refuse_all(status, n, st);
-    blu_hip *h0 = hs[0];
-    if (hipSetDevice(h0->device) != hipSuccess) return refuse_all(status, n, BLU_ERROR_DEVICE);
-    const int tr = (trans == 't' || trans == 'T') ? 1 : 0;
-
-    // per member, in the order of blu_hip_solve_sparse
-    std::vector<int> result(n, kPending), fresh, updated, lt;
-    for (int k = 0; k < n; k++) {
+        if (result[k] != kPending) continue;
         blu_hip *h = hs[k];
         if (h->nupdate < 0) { // solve_sparse.rs:46-47
             result[k] = BLU_ERROR_INVALID_CALL;
@@ -40,7 +33,7 @@ extern "C" int blu_hip_solve_sparse_batch(blu_hip **hs, int n, const int64_t *nz
             result[k] = BLU_ERROR_INVALID_ARGUMENT;
             continue;
         }
-        nzlhs[k] = 0;
+        if (gather[(size_t)k]) nzlhs[k] = 0;
         if (h->m == 0) {
             result[k] = BLU_OK;
             continue;
@@ -122,10 +115,28 @@ extern "C" int blu_hip_solve_sparse_batch(blu_hip **hs, int n, const int64_t *nz
     for (int k : R.list) {
         if (result[k] != BLU_OK) continue;
         take_solve_counters(hs[k], out[(size_t)k]);
-        if (out[(size_t)k].out[0] <= 0) continue;
+        if (out[(size_t)k].out[0] <= 0 || !gather[(size_t)k]) continue;
         got.push_back(k);
         off.push_back(off.back() + out[(size_t)k].out[0]);
     }
     gather_solutions(h0, hs, got, off, result, nzlhs, ilhs, lhs);
+}
+
+extern "C" int blu_hip_solve_sparse_batch(blu_hip **hs, int n, const int64_t *nzrhs, const uint64_t *const *irhs, const double *const *xrhs,
+                                          int64_t *nzlhs, int64_t *const *ilhs, double *const *lhs, char trans, int *status)
+{
+    // refusals of the call as a whole: every status[k] carries the code, no handle is touched
+    if (!hs || !nzrhs || !nzlhs || !ilhs || !lhs || n < 0) return refuse_all(status, n, BLU_ERROR_ARGUMENT_MISSING);
+    if (n == 0) return BLU_OK;
+    for (int k = 0; k < n; k++) {
+        if (!hs[k] || !ilhs[k] || !lhs[k]) return refuse_all(status, n, BLU_ERROR_ARGUMENT_MISSING);
+        if (nzrhs[k] > 0 && (!irhs || !xrhs || !irhs[k] || !xrhs[k])) return refuse_all(status, n, BLU_ERROR_ARGUMENT_MISSING);
+    }
+    if (const int st = batch_handles_refusal(hs, n); st != BLU_OK) return refuse_all(status, n, st);
+    blu_hip *h0 = hs[0];
+    if (hipSetDevice(h0->device) != hipSuccess) return refuse_all(status, n, BLU_ERROR_DEVICE);
+    std::vector<int> result(n, kPending);
+    solve_sparse_batch_core(h0, hs, n, nzrhs, irhs, xrhs, nzlhs, ilhs, lhs, (trans == 't' || trans == 'T') ? 1 : 0, std::vector<char>((size_t)n, 1),
+                            result);
     return batch_return(result, status);
 }

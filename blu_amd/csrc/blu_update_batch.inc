@@ -265,23 +265,18 @@ static void gather_solutions(blu_hip *h0, blu_hip **hs, const std::vector<int> &
     }
 }
 
-extern "C" int blu_hip_solve_for_update_batch(blu_hip **hs, int n, const int64_t *nzrhs, const uint64_t *const *irhs, const double *const *xrhs,
-                                              int64_t *nzlhs, int64_t *const *ilhs, double *const *lhs, char trans, int *status)
+// The call behind its refusals as a whole, for the members whose result[k] is still kPending: the checks of each member in
+// the order of blu_hip_solve_for_update, the storage-request loop, the counters.  want[k] != 0: member k's kernel leaves
+// the compressed solution in its sw.ilhs / sw.xval / sw.out[0] on the device; gather[k] != 0 (only with want[k]): it is
+// downloaded into nzlhs[k] / ilhs[k] / lhs[k] as well.  blu_hip_tableau_row_batch (blu_matrix_batch.inc) wants every
+// member's and gathers the ones its caller asked for.
+static void solve_for_update_batch_core(blu_hip *h0, blu_hip **hs, int n, const int64_t *nzrhs, const uint64_t *const *irhs,
+                                        const double *const *xrhs, int64_t *nzlhs, int64_t *const *ilhs, double *const *lhs, int tr,
+                                        const std::vector<char> &want, const std::vector<char> &gather, std::vector<int> &result)
 {
-    // refusals of the call as a whole: every status[k] carries the code, no handle is touched
-    const int tr = (trans == 't' || trans == 'T') ? 1 : 0;
-    if (!hs || !irhs || n < 0 || (!tr && (!xrhs || !nzrhs))) return refuse_all(status, n, BLU_ERROR_ARGUMENT_MISSING);
-    if (n == 0) return BLU_OK;
-    for (int k = 0; k < n; k++)
-        if (!irhs[k] || (!tr && !xrhs[k])) return refuse_all(status, n, BLU_ERROR_ARGUMENT_MISSING);
-    if (const int st = batch_handles_refusal(hs, n); st != BLU_OK) return refuse_all(status, n, st);
-    blu_hip *h0 = hs[0];
-    if (hipSetDevice(h0->device) != hipSuccess) return refuse_all(status, n, BLU_ERROR_DEVICE);
-    const bool want_any = nzlhs && ilhs && lhs;
-
-    // per member, in the order of blu_hip_solve_for_update
-    std::vector<int> result(n, kPending), active;
+    std::vector<int> active;
     for (int k = 0; k < n; k++) {
+        if (result[k] != kPending) continue;
         if (hs[k]->nupdate < 0) result[k] = BLU_ERROR_INVALID_CALL;     // solve_for_update.rs:85-86
         else if (hs[k]->m == 0) result[k] = BLU_ERROR_INVALID_ARGUMENT;
         else active.push_back(k);
@@ -312,8 +307,8 @@ extern "C" int blu_hip_solve_for_update_batch(blu_hip **hs, int n, const int64_t
             }
             UpdMember &M = mem[(size_t)k];
             memset(&M, 0, sizeof M);
-            M.want_solution = (want_any && ilhs[k] && lhs[k]) ? 1 : 0;
-            if (M.want_solution) nzlhs[k] = 0;
+            M.want_solution = want[(size_t)k] ? 1 : 0;
+            if (gather[(size_t)k]) nzlhs[k] = 0;
             M.nrhs = (int)nz;
             M.nz_sparse = (int)(h->sparse_thres * (double)h->m);
             rhs.off[(size_t)k] = rhs.ir.size();
@@ -333,11 +328,30 @@ extern "C" int blu_hip_solve_for_update_batch(blu_hip **hs, int n, const int64_t
     for (int k : active) {
         if (result[k] != BLU_OK) continue;
         take_solve_counters(hs[k], out[(size_t)k]);
-        if (!mem[(size_t)k].want_solution) continue;
+        if (!gather[(size_t)k]) continue;
         got.push_back(k);
         off.push_back(off.back() + out[(size_t)k].out[0]);
     }
     gather_solutions(h0, hs, got, off, result, nzlhs, ilhs, lhs);
+}
+
+extern "C" int blu_hip_solve_for_update_batch(blu_hip **hs, int n, const int64_t *nzrhs, const uint64_t *const *irhs, const double *const *xrhs,
+                                              int64_t *nzlhs, int64_t *const *ilhs, double *const *lhs, char trans, int *status)
+{
+    // refusals of the call as a whole: every status[k] carries the code, no handle is touched
+    const int tr = (trans == 't' || trans == 'T') ? 1 : 0;
+    if (!hs || !irhs || n < 0 || (!tr && (!xrhs || !nzrhs))) return refuse_all(status, n, BLU_ERROR_ARGUMENT_MISSING);
+    if (n == 0) return BLU_OK;
+    for (int k = 0; k < n; k++)
+        if (!irhs[k] || (!tr && !xrhs[k])) return refuse_all(status, n, BLU_ERROR_ARGUMENT_MISSING);
+    if (const int st = batch_handles_refusal(hs, n); st != BLU_OK) return refuse_all(status, n, st);
+    blu_hip *h0 = hs[0];
+    if (hipSetDevice(h0->device) != hipSuccess) return refuse_all(status, n, BLU_ERROR_DEVICE);
+    const bool want_any = nzlhs && ilhs && lhs;
+    std::vector<char> want((size_t)n, 0);
+    for (int k = 0; k < n; k++) want[(size_t)k] = (want_any && ilhs[k] && lhs[k]) ? 1 : 0;
+    std::vector<int> result(n, kPending);
+    solve_for_update_batch_core(h0, hs, n, nzrhs, irhs, xrhs, nzlhs, ilhs, lhs, tr, want, want, result);
     return batch_return(result, status);
 }
 

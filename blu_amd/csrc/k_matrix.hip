@@ -68,3 +68,107 @@ __global__ __launch_bounds__(ATD_THREADS) void k_at_dot(MatA A, const double *__
     }
     if (j < ncol) out[j] = s;
 }
+
+// ---------------------------------------------------------------------------------------------------------------------
+// The batched products (blu_matrix_batch.inc: blu_hip_tableau_row_batch, blu_hip_price_batch): many y against one A.
+//
+// The y vectors of a call are stored member-interleaved in groups of ATB_G = 8: the tile of group g holds
+// Y[g][i * 8 + t] for row i and member t of the group, so the eight y values of a row are one contiguous 64-byte piece.
+//
+//   k_scatter_lhs_batch   one workgroup per member: k_scatter_lhs of that member's compressed solution (the count read from
+//                         its sw.out[0] on the device) into its column of the tile, which the host has cleared
+//   k_at_dot_batch        out[member][j] = column j of A dotted with that member's y.  A group has nbx workgroups of the
+//                         grid behind each other (blockIdx.x / nbx is the group); a wave takes
+//                         a run of 64 consecutive columns, lane l column base + l, exactly as k_at_dot, but every entry
+//                         a_i[q] / a_x[q] it loads serves the eight members of the group: A is read once per group, not
+//                         once per member.  Each member keeps a sum of its own, s[t] = s[t] + a_x[q] * y_t[a_i[q]] in
+//                         storage order (n <= 64), or its own 64 strided partial sums and halving tree p[l] + p[l + w]
+//                         (n > 64): the chain of additions of a member is that of k_at_dot, so its bits are.
+// A skip is one byte per column per group, bit t for member t: that member's result is forced to +0.0; the column is
+// read unless every present member of the group skips it.  A last, partial group has zero y columns for its absent
+// members and does not store their rows.  ATB_G is chosen by reasoning ("Shared matrix, batched rows"): 64
+// bytes per gather is half a cache line, 16 + 16 VGPRs hold the sums and the y values, and A is fetched n / 8 times.
+// No result depends on it.
+#define ATB_G 8
+
+struct alignas(16) YRow {
+    double v[ATB_G];
+};
+struct ScatterSrc { // one member's compressed solution on the device
+    const long long *cnt;
+    const int *ilhs;
+    const double *xval;
+};
+
+__global__ __launch_bounds__(256) void k_scatter_lhs_batch(const ScatterSrc *__restrict__ src, int m, double *__restrict__ Y)
+{
+    const ScatterSrc S = src[blockIdx.x];
+    double *y = Y + (size_t)(blockIdx.x / ATB_G) * (size_t)m * ATB_G + (blockIdx.x % ATB_G);
+    const long long nz = min(S.cnt[0], (long long)m);
+    for (long long n = threadIdx.x; n < nz; n += blockDim.x) {
+        const int i = S.ilhs[n];
+        if ((unsigned)i < (unsigned)m) y[(size_t)i * ATB_G] = S.xval[n];
+    }
+}
+
+// c members in the chunk: groups 0 .. (c + 7) / 8 - 1, nbx workgroups each; mask may be NULL (no member skips anything)
+__global__ __launch_bounds__(ATD_THREADS) void k_at_dot_batch(MatA A, const double *__restrict__ Y, const unsigned char *__restrict__ mask,
+                                                              int ncol, int m, int c, int nbx, double *__restrict__ out)
+{
+    const int lane = (int)(threadIdx.x & 63);
+    const int g = (int)(blockIdx.x / (unsigned)nbx);
+    const long long base = ((long long)(blockIdx.x % (unsigned)nbx) * (ATD_THREADS / 64) + (long long)(threadIdx.x >> 6)) * 64;
+    if (base >= ncol) return; // (the whole wave)
+    const int present = min(ATB_G, c - g * ATB_G); // members of this group
+    const unsigned all = (1u << present) - 1u;
+    const YRow *__restrict__ yg = (const YRow *)(Y + (size_t)g * (size_t)m * ATB_G);
+    const long long j = base + lane;
+    unsigned sk = 0;
+    if (mask && j < ncol) sk = mask[(size_t)g * (size_t)ncol + (size_t)j];
+    const bool live = j < ncol && (sk & all) != all;
+    long long b = 0;
+    int n = 0;
+    if (live) {
+        b = A.ap[j];
+        n = (int)(A.ap[j + 1] - b);
+    }
+    double s[ATB_G];
+#pragma unroll
+    for (int t = 0; t < ATB_G; t++) s[t] = 0.0;
+    if (n <= 64)
+        for (int q = 0; q < n; q++) {
+            const double x = A.ax[b + q];
+            const YRow yr = yg[A.ai[b + q]];
+#pragma unroll
+            for (int t = 0; t < ATB_G; t++) s[t] = s[t] + x * yr.v[t];
+        }
+    unsigned long long longs = __ballot(n > 64);
+    while (longs) { // (wave-uniform)
+        const int l = __ffsll((long long)longs) - 1;
+        longs &= longs - 1;
+        const long long lb = A.ap[base + l];
+        const int ln = (int)(A.ap[base + l + 1] - lb);
+        double p[ATB_G];
+#pragma unroll
+        for (int t = 0; t < ATB_G; t++) p[t] = 0.0;
+        for (int q = lane; q < ln; q += 64) {
+            const double x = A.ax[lb + q];
+            const YRow yr = yg[A.ai[lb + q]];
+#pragma unroll
+            for (int t = 0; t < ATB_G; t++) p[t] = p[t] + x * yr.v[t];
+        }
+#pragma unroll
+        for (int t = 0; t < ATB_G; t++) {
+            double v = p[t];
+            // p[l] + p[l + w] for l < w; the result is lane 0's
+            for (int w = 32; w > 0; w >>= 1) v = v + __shfl_xor(v, w);
+            v = __shfl(v, 0);
+            if (lane == l) s[t] = v;
+        }
+    }
+    if (j < ncol) {
+#pragma unroll
+        for (int t = 0; t < ATB_G; t++)
+            if (t < present) out[(size_t)(g * ATB_G + t) * (size_t)ncol + (size_t)j] = ((sk >> t) & 1u) ? 0.0 : s[t];
+    }
+}

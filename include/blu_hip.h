@@ -421,6 +421,60 @@ int blu_hip_price(blu_hip *h, const double *y, const int64_t *skip, double *z);
  * [1] synchronizes, [2] host-to-device copies, [3] bytes downloaded. */
 int blu_hip_dbg_matrix_counts(const blu_hip *h, int64_t out[4]);
 
+/* Shared matrix, batched rows (no reference counterpart): the nodes a branch-and-bound code forks with blu_hip_copy_batch
+ * all work on one A.  blu_hip_share_matrix lets them hold one copy of it, and the two batch entries make the pivot rows and
+ * the pricing of all of them in one call.
+ *
+ * After blu_hip_share_matrix every dst[k] holds the matrix src holds: blu_hip_factorize_columns,
+ * blu_hip_solve_for_update_column, blu_hip_tableau_row, blu_hip_price and the two batch entries answer on dst[k] exactly as
+ * on a handle that had called blu_hip_set_matrix with the same arrays.  The device arrays of A and the host offsets exist
+ * once, in a reference-counted block; no device copy of A is made and nothing is launched.  Each destination gets the
+ * 8 m + 9 ncol bytes blu_hip_set_matrix allocates besides A; BLU_ERROR_OUT_OF_MEMORY there is that member's status, it is
+ * left without a matrix, and the others are shared regardless.  A destination that has a matrix, its own or a shared one,
+ * releases it first.  A holder leaves the block through blu_hip_free, through blu_hip_set_matrix (it gets a new matrix of
+ * its own) or through blu_hip_maxvolume (it answers BLU_ERROR_INVALID_CALL to the matrix entries afterwards, as any
+ * handle); the other holders keep the matrix, src being a holder like the others, and the last one frees the arrays.
+ * blu_hip_copy_batch in either role disturbs no holder and copies no matrix.
+ * Refused as a whole, every status[k] carrying the code and nothing touched: NULL src, dst or dst[k], or n < 0,
+ * BLU_ERROR_ARGUMENT_MISSING; src without a set matrix BLU_ERROR_INVALID_CALL; src among the destinations, a destination
+ * twice, on another device or with another m BLU_ERROR_INVALID_ARGUMENT.  n == 0 returns BLU_OK; status may be NULL; the
+ * return value is that of the other batch entries. */
+int blu_hip_share_matrix(blu_hip *src, blu_hip **dst, int n, int *status);
+/* handles that hold h's matrix, h included; 0 when none is set */
+int blu_hip_dbg_matrix_holders(const blu_hip *h);
+/* what tells one resident matrix from another: equal for the holders of one matrix, NULL when none is set */
+const void *blu_hip_dbg_matrix_id(const blu_hip *h);
+/* blu_hip_tableau_row(h[k], r[k], prepare_update, skip[k], alpha[k], ...) for n handles that hold one matrix, in one call:
+ * member k gets the status, the bits of every alpha[k][j] in the summation order above, +0.0 for skipped columns, the
+ * solution when asked for, the flop counters, the marker, the stored row eta and every later call of that single entry.
+ * prepare_update applies to every member.  skip may be NULL, and so may any skip[k].  If nzlhs, ilhs and lhs are all given,
+ * a member whose ilhs[k] and lhs[k] are non-NULL gets its solution (lhs[k] all zero on entry); otherwise it is not
+ * downloaded.  Fresh and updated members may be mixed.
+ * Step one is the batched transposed solve of its kind (blu_hip_solve_sparse_batch, blu_hip_solve_for_update_batch), the
+ * solutions staying on the device.  Step two, per chunk of members: the y vectors are scattered into tiles that interleave
+ * the members in groups of 8 (Y[i * 8 + t] for row i and member t), and one kernel reads every column of A once per group
+ * and keeps eight sums, each with the chain of additions of blu_hip_tableau_row; the products are downloaded in one copy.
+ * No result depends on the group size, on n, on a member's position or on the chunking.
+ * Refused as a whole: NULL h, r, alpha or h[k], NULL alpha[k] of a member with a matrix of ncol > 0, or n < 0,
+ * BLU_ERROR_ARGUMENT_MISSING; the same handle twice, two devices, or members with a set matrix that do not all hold the
+ * same one BLU_ERROR_INVALID_ARGUMENT (one unshared handle with n == 1 is fine).  n == 0 returns BLU_OK.
+ * Per member, in the order of the single entry, the others running regardless: BLU_ERROR_INVALID_CALL without a matrix,
+ * the refusals of its solve, BLU_ERROR_OUT_OF_MEMORY, BLU_ERROR_DEVICE; a failure of step two leaves the members as after
+ * their solves.
+ * Cost behind the solves, per chunk: one memset, one upload of descriptors, one of the skip masks if any member skips, two
+ * launches, one synchronize, one download of 8 ncol bytes per member -- none of them per member.  The device block of the
+ * tiles, products and masks is kept with the shared matrix, stays within 1 GiB and is freed with the last holder. */
+int blu_hip_tableau_row_batch(blu_hip **h, int n, const int64_t *r, int prepare_update, const int64_t *const *skip,
+                              double *const *alpha, int64_t *nzlhs, int64_t *const *ilhs, double *const *lhs, int *status);
+/* blu_hip_price(h[k], y[k], skip[k], z[k]) for n handles that hold one matrix, in one call: the y tiles are laid out on
+ * the host and uploaded, then the kernel, the download and the refusals of blu_hip_tableau_row_batch (NULL y[k] while
+ * m > 0 or NULL z[k] while ncol > 0: BLU_ERROR_ARGUMENT_MISSING).  Changes nothing observable on the handles. */
+int blu_hip_price_batch(blu_hip **h, int n, const double *const *y, const int64_t *const *skip, double *const *z, int *status);
+/* debug: the byte limit of the device block of the batched products of h's matrix (< 0: the default), so that small calls
+ * take several chunks; BLU_ERROR_INVALID_CALL without a set matrix.  After a batch call blu_hip_dbg_matrix_counts(h[0])
+ * reports its part behind the solves, summed over the chunks. */
+int blu_hip_dbg_set_matrix_batch_bytes(blu_hip *h, int64_t bytes);
+
 /* Copying a handle (no reference counterpart): the complete logical state of src goes into the n handles dst[0..n) of
  * the same m on the same device, so that many handles hold one factorization -- fresh or updated, a pending
  * blu_hip_solve_for_update included -- and the batch entries above can continue from it, each member its own way.

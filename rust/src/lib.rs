@@ -97,6 +97,15 @@ extern "C" {
     fn blu_hip_price(h: *mut BluHip, y: *const f64, skip: *const i64, z: *mut f64) -> c_int;
     fn blu_hip_dbg_matrix_counts(h: *const BluHip, out: *mut i64) -> c_int;
     fn blu_hip_copy_batch(src: *mut BluHip, dst: *mut *mut BluHip, n: c_int, status: *mut c_int) -> c_int;
+    fn blu_hip_share_matrix(src: *mut BluHip, dst: *mut *mut BluHip, n: c_int, status: *mut c_int) -> c_int;
+    fn blu_hip_dbg_matrix_holders(h: *const BluHip) -> c_int;
+    fn blu_hip_tableau_row_batch(
+        h: *mut *mut BluHip, n: c_int, r: *const i64, prepare_update: c_int, skip: *const *const i64, alpha: *const *mut f64, nzlhs: *mut i64,
+        ilhs: *const *mut i64, lhs: *const *mut f64, status: *mut c_int,
+    ) -> c_int;
+    fn blu_hip_price_batch(
+        h: *mut *mut BluHip, n: c_int, y: *const *const f64, skip: *const *const i64, z: *const *mut f64, status: *mut c_int,
+    ) -> c_int;
     fn blu_hip_clone(src: *mut BluHip) -> *mut BluHip;
     fn blu_hip_last_error(h: *const BluHip) -> *const c_char;
 }
@@ -529,6 +538,11 @@ impl BLU {
         out
     }
 
+    /// Objects that hold this object's resident matrix, itself included (`share_matrix`); 0 when none is set.
+    pub fn dbg_matrix_holders(&self) -> usize {
+        unsafe { blu_hip_dbg_matrix_holders(self.lu.h) as usize }
+    }
+
     // lu_clear_lhs, blu.rs:380-395
     fn clear_lhs(&mut self) {
         let nzsparse = (self.lu.sparse_thres() * self.m as f64) as usize;
@@ -733,6 +747,107 @@ pub fn copy_batch(src: &mut BLU, dsts: &mut [&mut BLU]) -> Result<Vec<Result<(),
             }
             b.nzlhs = 0;
         }
+    }
+    Ok(st.iter().map(|&s| status_of(s)).collect())
+}
+
+/// Every object of `dsts` (same `m`, same device) holds the resident matrix `src` holds afterwards (batch extension, no
+/// reference counterpart): one copy of `A` on the device for all of them, no device copy and no launch.  A destination
+/// that has a matrix lets go of it first; a holder leaves through `set_matrix`, `maxvolume` or by being dropped, and the
+/// last one frees the matrix.  `Err` is a refusal of the whole call (`src` without a matrix, another `m`, another device);
+/// otherwise one result per member.
+pub fn share_matrix(src: &mut BLU, dsts: &mut [&mut BLU]) -> Result<Vec<Result<(), Status>>, Status> {
+    let n = dsts.len();
+    let mut hs: Vec<*mut BluHip> = dsts.iter().map(|b| b.lu.h).collect();
+    let mut st = vec![0 as c_int; n];
+    let code = unsafe { blu_hip_share_matrix(src.lu.h, hs.as_mut_ptr(), n as c_int, st.as_mut_ptr()) };
+    if code == -3 || code == -4 || code == -2 {
+        return status_of(code).map(|_| Vec::new()); // (codes only a refusal returns)
+    }
+    for (k, b) in dsts.iter_mut().enumerate() {
+        if st[k] == 0 {
+            b.ncol = src.ncol;
+        }
+    }
+    Ok(st.iter().map(|&s| status_of(s)).collect())
+}
+
+/// `tableau_row(rows[k], prepare_update, skips[k], alphas[k])` for objects that hold one matrix (`share_matrix`) in one
+/// call: per member the status, the bits of `alpha`, the solution (left in `lhs` / `ilhs[..nzlhs]` with `want_solution`)
+/// and the statistics of the single call.  `Err` is a refusal of the whole call; otherwise one result per member.
+pub fn tableau_row_batch(
+    blus: &mut [&mut BLU], rows: &[usize], prepare_update: bool, skips: Option<&[Option<&[LUInt]>]>, alphas: &mut [&mut [f64]],
+    want_solution: bool,
+) -> Result<Vec<Result<(), Status>>, Status> {
+    let n = blus.len();
+    if rows.len() != n || alphas.len() != n || skips.map_or(false, |s| s.len() != n) {
+        return Err(Status::ErrorInvalidArgument);
+    }
+    for k in 0..n {
+        let ncol = blus[k].ncol.unwrap_or(0);
+        if alphas[k].len() < ncol || skips.map_or(false, |s| s[k].map_or(false, |x| x.len() < ncol)) {
+            return Err(Status::ErrorInvalidArgument);
+        }
+        if want_solution {
+            blus[k].clear_lhs();
+        }
+    }
+    let mut hs: Vec<*mut BluHip> = blus.iter().map(|b| b.lu.h).collect();
+    let r: Vec<i64> = rows.iter().map(|&x| x as i64).collect();
+    let sk: Vec<*const i64> = (0..n).map(|k| skips.and_then(|s| s[k]).map_or(std::ptr::null(), |x| x.as_ptr())).collect();
+    let al: Vec<*mut f64> = alphas.iter_mut().map(|a| a.as_mut_ptr()).collect();
+    let il: Vec<*mut i64> = blus.iter_mut().map(|b| b.ilhs.as_mut_ptr()).collect();
+    let xl: Vec<*mut f64> = blus.iter_mut().map(|b| b.lhs.as_mut_ptr()).collect();
+    let mut nz = vec![0i64; n];
+    let mut st = vec![0 as c_int; n];
+    let code = unsafe {
+        if want_solution {
+            blu_hip_tableau_row_batch(
+                hs.as_mut_ptr(), n as c_int, r.as_ptr(), prepare_update as c_int, sk.as_ptr(), al.as_ptr(), nz.as_mut_ptr(), il.as_ptr(), xl.as_ptr(),
+                st.as_mut_ptr(),
+            )
+        } else {
+            blu_hip_tableau_row_batch(
+                hs.as_mut_ptr(), n as c_int, r.as_ptr(), prepare_update as c_int, sk.as_ptr(), al.as_ptr(), std::ptr::null_mut(), std::ptr::null(),
+                std::ptr::null(), st.as_mut_ptr(),
+            )
+        }
+    };
+    // -3 is returned by a refusal alone; -4 is also a member's status (a row out of range): when every member carries it the
+    // call may have been refused (two devices, two matrices), and the members' results say the same
+    if code == -3 {
+        return status_of(code).map(|_| Vec::new());
+    }
+    for k in 0..n {
+        if st[k] == 0 && want_solution {
+            blus[k].nzlhs = nz[k] as usize;
+        }
+    }
+    Ok(st.iter().map(|&s| status_of(s)).collect())
+}
+
+/// `price(ys[k], skips[k], zs[k])` for objects that hold one matrix in one call; needs no factorization.
+pub fn price_batch(
+    blus: &mut [&mut BLU], ys: &[&[f64]], skips: Option<&[Option<&[LUInt]>]>, zs: &mut [&mut [f64]],
+) -> Result<Vec<Result<(), Status>>, Status> {
+    let n = blus.len();
+    if ys.len() != n || zs.len() != n || skips.map_or(false, |s| s.len() != n) {
+        return Err(Status::ErrorInvalidArgument);
+    }
+    for k in 0..n {
+        let ncol = blus[k].ncol.unwrap_or(0);
+        if ys[k].len() < blus[k].m || zs[k].len() < ncol || skips.map_or(false, |s| s[k].map_or(false, |x| x.len() < ncol)) {
+            return Err(Status::ErrorInvalidArgument);
+        }
+    }
+    let mut hs: Vec<*mut BluHip> = blus.iter().map(|b| b.lu.h).collect();
+    let py: Vec<*const f64> = ys.iter().map(|y| y.as_ptr()).collect();
+    let sk: Vec<*const i64> = (0..n).map(|k| skips.and_then(|s| s[k]).map_or(std::ptr::null(), |x| x.as_ptr())).collect();
+    let pz: Vec<*mut f64> = zs.iter_mut().map(|z| z.as_mut_ptr()).collect();
+    let mut st = vec![0 as c_int; n];
+    let code = unsafe { blu_hip_price_batch(hs.as_mut_ptr(), n as c_int, py.as_ptr(), sk.as_ptr(), pz.as_ptr(), st.as_mut_ptr()) };
+    if code == -3 || code == -4 {
+        return status_of(code).map(|_| Vec::new()); // (codes only a refusal returns)
     }
     Ok(st.iter().map(|&s| status_of(s)).collect())
 }

@@ -40,6 +40,14 @@
 //   OP_TABLEAU_ROW r prepare_update has_skip skip[ncol if has_skip] want status [alpha[ncol] [nzlhs ilhs[nzlhs] lhs[m] if want]
 //               if status == 0]                             blu_hip_tableau_row into an alpha of exactly ncol entries
 //   OP_PRICE has_skip skip[ncol if has_skip] y[m] status [z[ncol] if status == 0]          blu_hip_price
+//   OP_SHARE_MATRIX n                                       n new handles receive blu_hip_copy_batch from the current one and then
+//               blu_hip_share_matrix (every status BLU_OK expected); they replace the holders of an earlier record and are the
+//               members 1..n of the two records below, the current handle being member 0
+//   OP_TABLEAU_ROW_BATCH prepare_update bytes nmem {r has_skip skip[ncol if has_skip] want}[nmem] rc {status [alpha[ncol]
+//               [nzlhs ilhs[nzlhs] lhs[m] if want] if status == 0}[nmem]      blu_hip_tableau_row_batch over the first nmem
+//               members after blu_hip_dbg_set_matrix_batch_bytes(bytes), every alpha of exactly ncol entries
+//   OP_PRICE_BATCH bytes nmem {has_skip skip[ncol if has_skip] y[m]}[nmem] rc {status [z[ncol] if status == 0]}[nmem]
+//               blu_hip_price_batch likewise
 //   OP_END
 #include "../include/blu_hip.h"
 
@@ -56,16 +64,19 @@ extern "C" int blu_hip_dbg_set_multi_ws_bytes(blu_hip *h, int64_t bytes);
 extern "C" int blu_hip_dbg_set_sparse_multi_ws_bytes(blu_hip *h, int64_t bytes);
 // ... and of blu_hip_maxvolume (blu_maxvolume.inc)
 extern "C" int blu_hip_dbg_set_maxvolume_chunk(blu_hip *h, int64_t n);
+// ... and of the batched products with a shared matrix (blu_matrix_batch.inc)
+extern "C" int blu_hip_dbg_set_matrix_batch_bytes(blu_hip *h, int64_t bytes);
 
 enum { OP_END = 0, OP_NEW, OP_EXTRA, OP_PARAM, OP_FACT, OP_DENSE, OP_SPARSE, OP_FORUPD, OP_UPDATE, OP_STAT, OP_MULTI_WS, OP_DENSE_MULTI,
        OP_SPARSE_MULTI_WS, OP_SPARSE_MULTI, OP_SPARSE_MULTI_GET, OP_MAXVOLUME, OP_MAXVOLUME_CHUNK, OP_CLONE, OP_COPY_INTO, OP_SET_MATRIX,
-       OP_FACT_COLUMNS, OP_FORUPD_COLUMN, OP_TABLEAU_ROW, OP_PRICE };
+       OP_FACT_COLUMNS, OP_FORUPD_COLUMN, OP_TABLEAU_ROW, OP_PRICE, OP_SHARE_MATRIX, OP_TABLEAU_ROW_BATCH, OP_PRICE_BATCH };
 static const int64_t TAPE_MAGIC = 0x3145504154554c42LL; // "BLUTAPE1"
 static const char *const OP_NAME[] = {"end", "new", "dbg_set_upd_extra", "set_param", "factorize", "solve_dense", "solve_sparse",
                                       "solve_for_update", "update", "get_stat", "dbg_set_multi_ws_bytes", "solve_dense_multi",
                                       "dbg_set_sparse_multi_ws_bytes", "solve_sparse_multi", "get_sparse_multi", "maxvolume",
                                       "dbg_set_maxvolume_chunk", "clone", "copy_batch", "set_matrix", "factorize_columns",
-                                      "solve_for_update_column", "tableau_row", "price"};
+                                      "solve_for_update_column", "tableau_row", "price", "share_matrix", "tableau_row_batch",
+                                      "price_batch"};
 
 static std::vector<int64_t> tape;
 static size_t pos = 0;
@@ -149,9 +160,10 @@ int main(int argc, char **argv)
     blu_hip *h = nullptr;
     int64_t m = 0;
     size_t ncol = 0; // of the last OP_SET_MATRIX
+    std::vector<blu_hip *> holders; // of the last OP_SHARE_MATRIX
     for (;;) {
         op = word();
-        if (op < OP_END || op > OP_PRICE) {
+        if (op < OP_END || op > OP_PRICE_BATCH) {
             fprintf(stderr, "emu_replay: unknown record %lld after call %ld\n", (long long)op, ncall);
             return 2;
         }
@@ -397,6 +409,83 @@ int main(int argc, char **argv)
             }
             break;
         }
+        case OP_SHARE_MATRIX: {
+            for (blu_hip *k : holders) blu_hip_free(k);
+            holders.assign((size_t)word(), nullptr);
+            for (blu_hip *&k : holders) {
+                k = blu_hip_new(m, 1, 0);
+                same_int("handle", k != nullptr, 1);
+            }
+            std::vector<int> status(holders.size(), -99);
+            same_int("copy_batch", blu_hip_copy_batch(h, holders.data(), (int)holders.size(), status.data()), BLU_OK);
+            same_int("return value", blu_hip_share_matrix(h, holders.data(), (int)holders.size(), status.data()), BLU_OK);
+            for (int st : status) same_int("status", st, BLU_OK);
+            same_int("holders", blu_hip_dbg_matrix_holders(h), (int64_t)holders.size() + 1);
+            break;
+        }
+        case OP_TABLEAU_ROW_BATCH:
+        case OP_PRICE_BATCH: {
+            const bool rows = op == OP_TABLEAU_ROW_BATCH;
+            const int prepare = rows ? (int)word() : 0;
+            same_int("status", blu_hip_dbg_set_matrix_batch_bytes(h, word()), BLU_OK);
+            const size_t nmem = (size_t)word(), M = (size_t)m;
+            if (nmem > holders.size() + 1) {
+                fprintf(stderr, "emu_replay: call %ld (%s) has more members than holders\n", ncall, OP_NAME[op]);
+                return 2;
+            }
+            std::vector<blu_hip *> hs(1, h);
+            hs.insert(hs.end(), holders.begin(), holders.begin() + (long)(nmem - 1));
+            // (every host array of exactly the entries the call may touch)
+            std::vector<int64_t> r(nmem, 0), nzlhs(nmem, 0);
+            std::vector<char> want(nmem, 0);
+            std::vector<std::vector<int64_t>> skip(nmem), ilhs(nmem);
+            std::vector<std::vector<double>> y(nmem), out(nmem), lhs(nmem);
+            std::vector<const int64_t *> pskip(nmem, nullptr);
+            std::vector<const double *> py(nmem, nullptr);
+            std::vector<double *> pout(nmem), plhs(nmem, nullptr);
+            std::vector<int64_t *> pilhs(nmem, nullptr);
+            bool any_want = false;
+            for (size_t k = 0; k < nmem; k++) {
+                if (rows) r[k] = word();
+                if (word() != 0) {
+                    const int64_t *ts = take(ncol);
+                    skip[k].assign(ts, ts + ncol);
+                    pskip[k] = skip[k].data();
+                }
+                if (rows) {
+                    want[k] = word() != 0;
+                    if (want[k]) {
+                        ilhs[k].assign(M, 0);
+                        lhs[k].assign(M, 0.0);
+                        pilhs[k] = ilhs[k].data();
+                        plhs[k] = lhs[k].data();
+                        any_want = true;
+                    }
+                } else {
+                    const double *ty = (const double *)take(M);
+                    y[k].assign(ty, ty + M);
+                    py[k] = y[k].data();
+                }
+                out[k].assign(ncol, -7.25e300);
+                pout[k] = out[k].data();
+            }
+            std::vector<int> status(nmem, -99);
+            const int rc = rows ? blu_hip_tableau_row_batch(hs.data(), (int)nmem, r.data(), prepare, pskip.data(), pout.data(),
+                                                            any_want ? nzlhs.data() : nullptr, any_want ? pilhs.data() : nullptr,
+                                                            any_want ? plhs.data() : nullptr, status.data())
+                                : blu_hip_price_batch(hs.data(), (int)nmem, py.data(), pskip.data(), pout.data(), status.data());
+            same_int("return value", rc, word());
+            for (size_t k = 0; k < nmem; k++) {
+                same_int("status", status[k], word());
+                if (status[k] != BLU_OK) continue;
+                same_words(rows ? "alpha" : "z", out[k].data(), take(ncol), ncol, true);
+                if (!want[k]) continue;
+                same_int("nzlhs", nzlhs[k], word());
+                same_words("ilhs", ilhs[k].data(), take((size_t)nzlhs[k]), (size_t)nzlhs[k], false);
+                same_words("lhs", lhs[k].data(), take(M), M, true);
+            }
+            break;
+        }
         case OP_STAT: {
             const int key = (int)word();
             const double got = blu_hip_get_stat(h, key);
@@ -407,6 +496,7 @@ int main(int argc, char **argv)
         }
         }
     }
+    for (blu_hip *k : holders) blu_hip_free(k);
     if (h) blu_hip_free(h);
     printf("REPLAY OK: %ld calls\n", ncall);
     return 0;
