@@ -133,6 +133,8 @@ static void copy_host_state(const blu_hip *src, blu_hip *d, bool with_upd)
     d->relaunches = src->relaunches;
     d->last_pivot_kernel = src->last_pivot_kernel;
     d->last_pivot_regs = src->last_pivot_regs;
+    d->last_addr_wide = src->last_addr_wide;
+    d->narrow_launches = src->narrow_launches;
     // caches keyed by nfactorize: the update workspace came with its key, the row-wise copies are rebuilt on demand
     d->upd_for_nfact = with_upd ? d->nfactorize : -1;
     d->lt_for_nfact = d->rows_for_nfact = -1;

@@ -238,6 +238,102 @@ typedef LinkField<LINEREC_BLINK, 4> LinkB;
         ccap{(GPTR(char))crec}, rcap{(GPTR(char))rrec}, colmax{(GPTR(char))crec},                        \
         cflink{(GPTR(char))crec, (GPTR(char))chead, m}, rflink{(GPTR(char))rrec, (GPTR(char))rhead, m},  \
         cblink{(GPTR(char))crec, (GPTR(char))chead, m}, rblink{(GPTR(char))rrec, (GPTR(char))rhead, m}
+// ---- 32-bit offsets off a scalar base (the descriptor view of k_pivot_loop: DevGPDietT<true> below) --------------------
+// base[i] with an int index into a global pointer sign-extends the index and computes a 64-bit address in a vector
+// register pair for every access (v_ashrrev_i32 + v_lshl_add_u64, then global_load v[a:b], off).  With the BYTE OFFSET
+// computed in 32 bits and zero-extended the access is one v_lshlrev_b32 and global_load v_off, s[base:base+1]: no sign
+// extension, no 64-bit operation, no register pair.  Valid while the index is non-negative and every byte extent of the
+// array is below 2^32: the host takes k_pivot_loop_w64 (today's addressing) for a launch where that does not hold
+// (addr32_fits, blu_driver.inc).  Three builds of the offset, selected the way uniform_here is:
+//   product        no check
+//   BLU_EMU_BUILD  (host) assert that the index is non-negative and the offset below the limit of the launch
+//   BLU_EWCHECK    (self-checking GPU build) a negative index or an offset that does not fit becomes offset 0 and the error
+//                  is recorded like a failed DEV_CHECK of the pivot loop (ST_ERROR at the next pivot boundary): a wrapped
+//                  offset would land 4 GB behind the base, where the old form read the element in front of the array
+#if defined(BLU_EMU_BUILD)
+#include <assert.h>
+static unsigned long long g_emu_addr32_limit = 1ull << 32; // set by the host in front of every narrow launch
+__device__ __forceinline__ unsigned addr32_off(int i, unsigned size)
+{
+    assert(i >= 0);
+    assert((unsigned long long)(unsigned)i * size < g_emu_addr32_limit);
+    return (unsigned)i * size;
+}
+#elif defined(BLU_EWCHECK)
+__shared__ int g_addr32_err_line; // k_pivot_loop zeroes it, looks at it at every loop head and reports it when it leaves
+__device__ __forceinline__ unsigned addr32_off(int i, unsigned size)
+{
+    if (i < 0 || ((unsigned long long)(unsigned)i * size) >> 32) {
+        g_addr32_err_line = __LINE__;
+        return 0u;
+    }
+    return (unsigned)i * size;
+}
+#else
+__device__ __forceinline__ unsigned addr32_off(int i, unsigned size) { return (unsigned)i * size; }
+#endif
+template <class T> struct Arr32 {
+    GPTR(T) base; // wave-uniform: a scalar register pair
+    __device__ __forceinline__ __attribute__((address_space(1))) T &operator[](int i) const
+    {
+        return *(GPTR(T))((GPTR(char))base + (size_t)addr32_off(i, (unsigned)sizeof(T)));
+    }
+    // the array from element i on as an ordinary pointer, for a helper that takes one (today's form)
+    __device__ __forceinline__ GPTR(T) operator+(int i) const { return base + i; }
+    __device__ __forceinline__ operator GPTR(T)() const { return base; }
+};
+// RecField / LinkField in that form.  The record's offset is computed in 32 bits and zero-extended; the field's constant
+// offset is added BEHIND the zero-extension, so that it becomes the immediate offset of the instruction (inside the 32-bit
+// expression the compiler falls back to a 64-bit add for the second field of one record).
+template <class T, int OFF> struct RecField32 {
+    GPTR(char) base;
+    __device__ __forceinline__ __attribute__((address_space(1))) T &operator[](int i) const
+    {
+        return *(GPTR(T))(base + (size_t)addr32_off(i, (unsigned)sizeof(LineRec)) + OFF);
+    }
+};
+// (Not kept: the head array reached as the record array plus a 32-bit byte offset -- both live in the slab --, so that the
+// per-lane choice below is a select between two 32-bit offsets off ONE scalar base instead of a 64-bit select and a vector
+// address.  It took 629 static vector instructions and 198 reloads out of the kernel, and the step was 645.17 ms against
+// 644.66: DESIGN.md section 4, profiles/addr32_ab.txt.)
+template <int OFF, int HOFF> struct LinkField32 {
+    GPTR(char) rec;
+    GPTR(char) head;
+    int m;
+    // (the select between two bases leaves this one access with a vector base; both offsets are 32-bit)
+    __device__ __forceinline__ __attribute__((address_space(1))) int &operator[](int x) const
+    {
+        GPTR(char) p = x < m ? rec + (size_t)addr32_off(x, (unsigned)sizeof(LineRec)) + OFF : head + (size_t)addr32_off(x - m, (unsigned)sizeof(HeadRec)) + HOFF;
+        return *(GPTR(int))p;
+    }
+    __device__ __forceinline__ __attribute__((address_space(1))) int &el(int x) const
+    {
+        return *(GPTR(int))(rec + (size_t)addr32_off(x, (unsigned)sizeof(LineRec)) + OFF);
+    }
+    __device__ __forceinline__ __attribute__((address_space(1))) int &hd(int k) const
+    {
+        return *(GPTR(int))(head + (size_t)addr32_off(k, (unsigned)sizeof(HeadRec)) + HOFF);
+    }
+};
+// the view types of a kernel family by its addressing: NARROW = the 32-bit forms
+template <bool NARROW> struct AddrForms {
+    template <class T> struct Arr { typedef GPTR(T) type; };
+    typedef ::RecBeg RecBeg;
+    typedef ::RecLen RecLen;
+    typedef ::RecCap RecCap;
+    typedef ::RecMax RecMax;
+    typedef ::LinkF LinkF;
+    typedef ::LinkB LinkB;
+};
+template <> struct AddrForms<true> {
+    template <class T> struct Arr { typedef Arr32<T> type; };
+    typedef RecField32<int, LINEREC_BEG> RecBeg;
+    typedef RecField32<int, LINEREC_LEN> RecLen;
+    typedef RecField32<int, LINEREC_CAP> RecCap;
+    typedef RecField32<double, LINEREC_MAX> RecMax;
+    typedef LinkField32<LINEREC_FLINK, 0> LinkF;
+    typedef LinkField32<LINEREC_BLINK, 4> LinkB;
+};
 // atomics on global-address-space pointers (the HIP atomicAdd/atomicMin overloads take generic pointers)
 __device__ __forceinline__ int g_atomic_add(gint_p p, int v)
 {
@@ -283,6 +379,22 @@ template <class T> struct ColdArr {
     __device__ __forceinline__ __attribute__((address_space(1))) T &operator[](size_t i) const { return get()[i]; }
     __device__ __forceinline__ GPTR(T) operator+(int i) const { return get() + i; }
 };
+// ColdArr of the narrow view: the int index goes in the 32-bit form behind the scalar load of the base.  (An index given as
+// size_t -- the dense work columns in gwork, 16 * (m + 1) doubles -- keeps the 64-bit form.)
+template <class T> struct ColdArr32 {
+    typedef T *ptr_t;
+    const __attribute__((address_space(1))) ptr_t *slot;
+    __device__ __forceinline__ GPTR(T) get() const { return (GPTR(T))(*slot); }
+    __device__ __forceinline__ operator GPTR(T)() const { return get(); }
+    __device__ __forceinline__ __attribute__((address_space(1))) T &operator[](int i) const
+    {
+        return *(GPTR(T))((GPTR(char))get() + (size_t)addr32_off(i, (unsigned)sizeof(T)));
+    }
+    __device__ __forceinline__ __attribute__((address_space(1))) T &operator[](size_t i) const { return get()[i]; }
+    __device__ __forceinline__ GPTR(T) operator+(int i) const { return get() + i; }
+};
+template <class T, bool NARROW> struct ColdArrOf { typedef ColdArr<T> type; };
+template <class T> struct ColdArrOf<T, true> { typedef ColdArr32<T> type; };
 // The same for the parameters and capacities: held by value they are ~20 more scalar registers live across the whole pivot
 // loop (the four tolerances alone are eight), spilled and reloaded lane by lane wherever one is used.  A ColdVal reads its
 // word from the descriptor where it is used: one load through the scalar cache (constant address space: the descriptor is
@@ -301,8 +413,9 @@ template <class T> struct ColdVal {
     __device__ __forceinline__ operator T() const { return *slot; }
 };
 // And of the HOT arrays, the six that a pivot touches once or twice, in its finalize step, are fetched like the COLD ones;
-// the line records, the arenas and the factors stay in registers.  (The slab residents as 32-bit offsets from one base, and
-// array indices zero-extended through an accessor, were not built.)
+// the line records, the arenas and the factors stay in registers.  In the narrow view every one of them is indexed by a
+// 32-bit byte offset off its scalar base (Arr32, RecField32, ColdArr32 above).  (The slab residents as 32-bit offsets from
+// ONE base: the link views were built so and not kept, see LinkField32; the rest was not built.  DESIGN.md section 4.)
 #define DEVLU_ARRAYS_PIVOT_FETCHED(X) X(int, pinv) X(int, qinv) X(int, prow) X(int, pcol) X(int, lbeg) X(int, ubeg)
 #define DEVLU_ARRAYS_PIVOT_HELD(X)                                                                     \
     X(LineRec, crec) X(LineRec, rrec) X(HeadRec, chead) X(HeadRec, rhead)                              \
@@ -342,25 +455,32 @@ struct DevGP {
     {
     }
 };
-// The view of k_pivot_loop (one basis, sixteen waves): see ColdVal and DEVLU_ARRAYS_PIVOT_FETCHED above;
-// k_pivot_view.h names it DevGP inside the namespace of that kernel.
-struct DevGPDiet {
+// The view of k_pivot_loop (one basis, sixteen waves): see ColdVal and DEVLU_ARRAYS_PIVOT_FETCHED above.  NARROW = arrays and
+// line views in the 32-bit offset form (k_pivot_loop), else today's pointers (k_pivot_loop_w64, for storage of 4 GB and
+// more).  k_pivot_view.h names it DevGP inside the namespace of each of the two kernels.
+template <bool NARROW> struct DevGPDietT {
+    typedef AddrForms<NARROW> AF;
 #define X(T, n) T n;
     DEVLU_SCALARS_HELD(X)
 #undef X
 #define X(T, n) ColdVal<T> n;
     DEVLU_SCALARS_COLD(X)
 #undef X
-#define X(T, n) GPTR(T) n;
+#define X(T, n) typename AF::template Arr<T>::type n;
     DEVLU_ARRAYS_PIVOT_HELD(X)
 #undef X
-#define X(T, n) ColdArr<T> n;
+#define X(T, n) typename ColdArrOf<T, NARROW>::type n;
     DEVLU_ARRAYS_PIVOT_FETCHED(X)
     DEVLU_ARRAYS_COLD(X)
 #undef X
     Scalars *s;
-    DEV_LINE_VIEWS
-    __device__ __forceinline__ explicit DevGPDiet(const DevLU *d)
+    typename AF::RecBeg cbeg, rbeg;
+    typename AF::RecLen clen, rlen;
+    typename AF::RecCap ccap, rcap;
+    typename AF::RecMax colmax;
+    typename AF::LinkF cflink, rflink;
+    typename AF::LinkB cblink, rblink;
+    __device__ __forceinline__ explicit DevGPDietT(const DevLU *d)
         :
 #define X(T, n) n(d->n),
           DEVLU_SCALARS_HELD(X)
@@ -368,15 +488,18 @@ struct DevGPDiet {
 #define X(T, n) n{(const __attribute__((address_space(4))) T *)&d->n},
           DEVLU_SCALARS_COLD(X)
 #undef X
-#define X(T, n) n((GPTR(T))d->n),
+#define X(T, n) n{(GPTR(T))d->n},
               DEVLU_ARRAYS_PIVOT_HELD(X)
 #undef X
-#define X(T, n) n{(const __attribute__((address_space(1))) ColdArr<T>::ptr_t *)&d->n},
+#define X(T, n) n{(const __attribute__((address_space(1))) typename ColdArr<T>::ptr_t *)&d->n},
                   DEVLU_ARRAYS_PIVOT_FETCHED(X)
                   DEVLU_ARRAYS_COLD(X)
 #undef X
                       s(d->s),
-          DEV_LINE_VIEWS_INIT
+          cbeg{(GPTR(char))d->crec}, rbeg{(GPTR(char))d->rrec}, clen{(GPTR(char))d->crec}, rlen{(GPTR(char))d->rrec},
+          ccap{(GPTR(char))d->crec}, rcap{(GPTR(char))d->rrec}, colmax{(GPTR(char))d->crec},
+          cflink{(GPTR(char))d->crec, (GPTR(char))d->chead, d->m}, rflink{(GPTR(char))d->rrec, (GPTR(char))d->rhead, d->m},
+          cblink{(GPTR(char))d->crec, (GPTR(char))d->chead, d->m}, rblink{(GPTR(char))d->rrec, (GPTR(char))d->rhead, d->m}
     {
     }
 };

@@ -59,6 +59,7 @@ struct BatchCtx {
     hipEvent_t pe2[2] = {nullptr, nullptr};
     hipEvent_t pe[2] = {nullptr, nullptr};
     int relaunches = 0;
+    int narrow_launches = 0; // launches of k_pivot_loop with 32-bit addressing (statistic 130)
     char *fill_scr = nullptr; // k_finish of a batch: scratch of fill_scr_bytes per workgroup for its fill through buckets (k_bucket.h)
     long long fill_scr_bytes = 0;
     void phase_begin() { (void)hipEventRecord(pe[0], stream); }
@@ -126,6 +127,7 @@ static void batch_release(BatchCtx &B)
         h->t_total = B.t_total;
         for (int q = 0; q < 6; q++) h->t_phase[q] = B.t_phase[q];
         h->relaunches = B.relaunches;
+        h->narrow_launches = B.narrow_launches;
     }
     if (B.owns_arrays) {
         dfree(B.dD);
@@ -294,7 +296,16 @@ static bool batch_pivot_and_finish(BatchCtx &B)
             }
         } else {
             which = 0; // (one basis)
-            hipLaunchKernelGGL(k_pivot_loop, dim3(n), dim3(B.block_pivot), 0, B.stream, B.dD, (int)h0->stop_at);
+            h0->last_addr_wide = addr32_fits(h0) ? 0 : 1;
+            if (h0->last_addr_wide) {
+                hipLaunchKernelGGL(k_pivot_loop_w64, dim3(n), dim3(B.block_pivot), 0, B.stream, B.dD, (int)h0->stop_at);
+            } else {
+#ifdef BLU_EMU_BUILD
+                g_emu_addr32_limit = h0->addr32_limit; // (what the asserting accessor checks)
+#endif
+                B.narrow_launches++;
+                hipLaunchKernelGGL(k_pivot_loop, dim3(n), dim3(B.block_pivot), 0, B.stream, B.dD, (int)h0->stop_at);
+            }
         }
         for (int k = 0; k < n; k++) B.hs[k]->last_pivot_kernel = which, B.hs[k]->last_pivot_regs = regs;
         (void)hipEventRecord(B.ev[3], B.stream);

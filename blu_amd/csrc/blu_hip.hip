@@ -22,6 +22,13 @@
 #include "k_pivot.hip"
 #undef BLU_NS
 #undef BLU_CFG_WAVE
+#define BLU_NS pv_single_w64 // the same kernel with 64-bit addressing (k_pivot_view.h): k_pivot_loop_w64
+#define BLU_CFG_WAVE 0
+#define BLU_ADDR_WIDE 1
+#include "k_pivot.hip"
+#undef BLU_NS
+#undef BLU_CFG_WAVE
+#undef BLU_ADDR_WIDE
 #define BLU_NS pv_wave
 #define BLU_CFG_WAVE 1
 #include "k_pivot.hip"
@@ -33,6 +40,7 @@
 #undef BLU_NS
 #undef BLU_CFG_WAVE
 using pv_single::k_pivot_loop;
+using pv_single_w64::k_pivot_loop_w64;
 using pv_wave::k_pivot_loop_wave;
 using pv_wave::k_pivot_loop_wave_r3;
 using pv_wave2::k_pivot_loop_wave2;
@@ -182,6 +190,10 @@ struct blu_hip {
     GridWs *gw;        // scratch of the chip-wide O(nnz) phases (single-basis path)
     int grid_blocks;   // workgroups of their cooperative launches (0/1: one workgroup, as in a batch)
     int last_pivot_kernel, last_pivot_regs; // (statistics 118, 120)
+    unsigned long long addr32_limit; // k_pivot_loop addresses its arrays by 32-bit byte offsets while every extent is below this (env BLU_ADDR32_LIMIT; 0: never)
+    size_t slab_bytes;               // size of the slab
+    int last_addr_wide;              // (statistic 129) the last launch of k_pivot_loop: 0 narrow, 1 k_pivot_loop_w64
+    int narrow_launches;             // (statistic 130) launches of the last factorize that were narrow (of `relaunches`)
     int lds_window, lds_window_mode; // bytes of dynamic LDS the batch forms of k_prep / k_finish may use as a counter window (0: not available), and when (env BLU_LDS_WINDOW)
     int num_cus, batch_grid; // CUs of the device; workgroups of k_prep / k_setup / k_finish in a batch (0: one per CU; env BLU_BATCH_GRID)
     int wave2_max;     // bases the card holds at once with TWO waves each (k_pivot_loop_wave2): a batch up to this size takes that kernel
@@ -290,6 +302,27 @@ static bool set_status(blu_hip *h, int st)
 {
     HIP_TRY(h, hipMemcpy(&h->D.s->status, &st, sizeof(int), hipMemcpyHostToDevice));
     return true;
+}
+
+// The largest byte extent an int index of k_pivot_loop reaches in the line records and in the storage that grows: the two
+// arenas and the factors.  (The dense work columns in gwork are indexed by size_t, in 64 bits; the packed copies of B are not
+// touched by the pivot loop.)
+static unsigned long long addr32_max_extent(const blu_hip *h)
+{
+    const DevLU &D = h->D;
+    const unsigned long long ext[] = {(unsigned long long)h->m * sizeof(LineRec), (unsigned long long)D.carena_cap * sizeof(double),
+                                      (unsigned long long)D.rarena_cap * sizeof(int), (unsigned long long)D.lcap * sizeof(double),
+                                      (unsigned long long)D.ucap * sizeof(double)};
+    return *std::max_element(ext, ext + sizeof ext / sizeof ext[0]);
+}
+// May this launch of k_pivot_loop address the arrays by 32-bit byte offsets (blu_dev.h: Arr32)?  Every such extent below the
+// limit of the handle, and the slab -- every array of m + 2 elements lives in it, and it never grows -- below 2^32: the slab is
+// not compared with the diagnostic limit, or no limit could be crossed by growth on a small basis, where the slab is the
+// largest allocation (m = 300: 67 KB against a column arena of 34 KB that grows to 53 KB).
+// Asked before EVERY launch: storage grows between two launches of one factorize.
+static bool addr32_fits(const blu_hip *h)
+{
+    return addr32_max_extent(h) < h->addr32_limit && (unsigned long long)h->slab_bytes < (1ull << 32);
 }
 
 // ---------------------------------------------------------------------------------------------
@@ -426,6 +459,7 @@ extern "C" blu_hip *blu_hip_new(int64_t m, int64_t b_nz, int device)
     want(&D.s, 1); want(&h->dD, 1); want(&h->dO, 1); want(&h->gw, 1);
     want(&h->O.rowperm, M); want(&h->O.colperm, M); want(&h->O.l_colptr, M + 1); want(&h->O.u_colptr, M + 1);
     ok = ok && dalloc(h, &h->slab, slab_bytes);
+    h->slab_bytes = slab_bytes;
     if (ok)
         for (auto &r : reqs) *r.first = (void *)(h->slab + r.second);
     ok = ok && dalloc(h, &D.bc_idx, D.nzcap) && dalloc(h, &D.bc_val, D.nzcap) && dalloc(h, &D.bt_idx, D.nzcap) && dalloc(h, &D.bt_val, D.nzcap);
@@ -450,6 +484,10 @@ extern "C" blu_hip *blu_hip_new(int64_t m, int64_t b_nz, int device)
         const char *pk = getenv("BLU_PIVOT_KERNEL");
         h->pivot_kernel = pk ? atoi(pk) : 0;
         if (h->pivot_kernel != 1 && h->pivot_kernel != 3) h->pivot_kernel = 0;
+        // BLU_ADDR32_LIMIT: bytes; every extent below it = the narrow k_pivot_loop.  Default and ceiling 2^32, 0 = always wide
+        h->addr32_limit = 1ull << 32;
+        if (const char *al = getenv("BLU_ADDR32_LIMIT")) h->addr32_limit = std::min<unsigned long long>(strtoull(al, nullptr, 10), 1ull << 32);
+        h->last_addr_wide = h->narrow_launches = 0;
     }
     if (ok) { // chip-wide phases: as many workgroups as are certainly co-resident, at most 64 (one per CU of two XCDs' worth)
         int nb = 0, best = 1 << 30;
@@ -640,6 +678,9 @@ extern "C" double blu_hip_get_stat(const blu_hip *h, int key)
     case 115: return (double)h->D.lcap;
     case 120: return (double)h->last_pivot_regs; // waves per SIMD its register budget was set for (the _r3 variants of the wave kernels: 3; else 4)
     case 118: return (double)h->last_pivot_kernel; // which pivot kernel the last factorize of this handle ran: 0 k_pivot_loop, 1 k_pivot_loop_wave, 3 k_pivot_loop_wave2 (2 is not used)
+    case 129: return (double)h->last_addr_wide; // addressing of the last launch of k_pivot_loop: 0 narrow (32-bit offsets), 1 wide (k_pivot_loop_w64)
+    case 130: return (double)h->narrow_launches; // launches of k_pivot_loop in the last factorize that were narrow (of BLU_STAT_DEV_RELAUNCHES: storage grown between two launches can cross the limit)
+    case 151: return (double)addr32_max_extent(h); // bytes: what BLU_ADDR32_LIMIT is compared with before a launch of k_pivot_loop (line records, arenas, factors: grows with the storage)
     case 119: return (double)s.fill_paths; // bit 0 / bit 1: k_prep / k_finish filled through buckets (k_bucket.h)
     case 121: case 122: return (double)s.nrun[key - 121]; // k_pivot_loop, singleton-column pivots: search found early / set-up done early as well (two barriers instead of three)
     case 123: return (double)s.nrun[2]; // k_pivot_loop, barrier merged as for 122: small pivots set up during the finalize step of their predecessor

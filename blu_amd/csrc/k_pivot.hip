@@ -562,7 +562,7 @@ __device__ __forceinline__ void gen_update_col(const DevGP &D, Sm *sm, int q, bo
 
     // update and append in pivot-column order
     const double a = xrj / pivot;
-    const int put = dst + nk1;
+    const int put = dst + nk1; // (nk1 >= 0: the column holds the pivot row's entry, checked above -- Arr32 wants a non-negative index)
     int nadd = 0;
     unsigned long long mask = 0;
     if (small) {
@@ -1289,6 +1289,9 @@ __device__ __forceinline__ void pivot_loop_body(DevLU *Ds, int stop_at, Sm *sm, 
     if (tid == 0) {
         g_pivot_err = 0;
         g_pivot_err_line = 0;
+#ifdef BLU_EWCHECK
+        g_addr32_err_line = 0; // (the index check of the 32-bit accessors, blu_dev.h)
+#endif
     }
     mc_reset(D, mc, tid, (int)blockDim.x);
     __syncthreads();
@@ -1403,6 +1406,9 @@ __device__ __forceinline__ void pivot_loop_body(DevLU *Ds, int stop_at, Sm *sm, 
         if (w == 0) {
             // ---- loop head: done / stop / error?
             if (LANE_IS0(lane)) {
+#ifdef BLU_EWCHECK
+                if (g_addr32_err_line) probe_overrun(g_addr32_err_line);
+#endif
                 if (g_pivot_err) sm->exit_code = ST_ERROR;
                 else if (sm->rank + sm->rankdef >= m) sm->exit_code = ST_DONE;
                 else if (sm->stop_at >= 0 && sm->pc < 0 && sm->rank + sm->rankdef >= sm->stop_at) sm->exit_code = ST_STOPPED;
@@ -1587,13 +1593,23 @@ __device__ __forceinline__ void pivot_loop_body(DevLU *Ds, int stop_at, Sm *sm, 
         for (int k = 0; k < 48; k++) S->prof[k] += sm->prof[k];
         for (int k = 0; k < 20; k++) S->prof2[k] += sm->prof2[k];
 #endif
+#ifdef BLU_EWCHECK
+        if (g_addr32_err_line) { // (an index refused after the last loop head as well)
+            sm->exit_code = ST_ERROR;
+            g_pivot_err_line = g_addr32_err_line;
+        }
+#endif
         if (sm->exit_code == ST_ERROR && g_pivot_err_line) set_error(S, ST_ERROR, g_pivot_err_line);
         if (S->status == ST_RUNNING) S->status = sm->exit_code;
     }
 }
 
-// One matrix: all 16 waves of a CU, 128 VGPRs.
+// One matrix: all 16 waves of a CU, 128 VGPRs.  (_w64: the instantiation with 64-bit addressing, k_pivot_view.h)
+#if BLU_ADDR_WIDE
+__global__ void __launch_bounds__(1024) k_pivot_loop_w64(DevLU *Ds, int stop_at)
+#else
 __global__ void __launch_bounds__(1024) k_pivot_loop(DevLU *Ds, int stop_at)
+#endif
 {
     __shared__ Sm smem;
     __shared__ Mc mcache;

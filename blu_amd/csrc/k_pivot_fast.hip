@@ -1135,7 +1135,7 @@ __device__ __forceinline__ void fast_col(const DevGP &D, Sm *sm, Mc *mc, Fast *f
         D.cval[dst + where - 1] = first_val;
     }
     const double a = xrj / pivot;
-    const int put = dst + nk1;
+    const int put = dst + nk1; // (nk1 >= 0: the column holds the pivot row's entry, checked above -- Arr32 wants a non-negative index)
     const bool p = lane < cnz1;
     double x = 0.0;
     int ri = 0;
@@ -1232,7 +1232,7 @@ __device__ __forceinline__ void fast_col_short(const DevGP &D, Sm *sm, Mc *mc, F
         D.cval[dst + where - 1] = first_val;
     }
     const double a = xrj / pivot;
-    const int put = dst + nk1;
+    const int put = dst + nk1; // (nk1 >= 0: the column holds the pivot row's entry, checked above -- Arr32 wants a non-negative index)
     const bool p = lane < cnz1;
     double x = 0.0;
     int ri = 0;

@@ -78,3 +78,7 @@ STAT_UPDATE_COST = 124
 # Device-only diagnostics like 121..126, which have no names here: not STAT_*, the names of what the oracle answers as well.
 DEVSTAT_SETUP_TWO_WAVES = 127   # set-ups of small pivots completed on two waves (equals statistic 123)
 DEVSTAT_SETUP_ABANDONED = 128   # hand-overs between the two waves that ran into the bound of a wait (a defect: 0)
+DEVSTAT_ADDR_WIDE = 129         # addressing of the last launch of k_pivot_loop: 0 narrow (32-bit offsets), 1 wide (k_pivot_loop_w64; env BLU_ADDR32_LIMIT)
+DEVSTAT_NARROW_LAUNCHES = 130   # launches of k_pivot_loop in the last factorize that were narrow (of STAT_DEV_RELAUNCHES)
+DEVSTAT_ADDR_EXTENT = 151       # bytes: the largest extent an int index of k_pivot_loop reaches now (line records, arenas, factors);
+                                # narrow while it is below BLU_ADDR32_LIMIT (131..150 are the diagnostic build's)
