@@ -57,6 +57,8 @@ EXPORTS = [
     "blu_hip_solve_sparse_multi", "blu_hip_get_sparse_multi", "blu_hip_maxvolume",
     "blu_hip_copy_batch", "blu_hip_clone",
     "blu_hip_set_matrix", "blu_hip_factorize_columns", "blu_hip_solve_for_update_column", "blu_hip_tableau_row", "blu_hip_price",
+    "blu_hip_set_duals", "blu_hip_get_duals", "blu_hip_get_ratio_row", "blu_hip_ratio_test", "blu_hip_update_duals",
+    "blu_hip_copy_duals_batch", "blu_hip_ratio_test_batch", "blu_hip_update_duals_batch",
 ]
 
 
@@ -483,6 +485,113 @@ def price_batch(handles, ys, skips=None):
     return out, zs
 
 
+class RatioResult(C.Structure):
+    """blu_ratio_result (include/blu_hip.h)"""
+    _fields_ = [("q", C.c_int64), ("ncand", C.c_int64), ("alpha_q", C.c_double), ("d_q", C.c_double), ("step", C.c_double),
+                ("bound", C.c_double), ("reserved", C.c_int64 * 2)]
+
+    def as_tuple(self):
+        """(q, ncand, alpha_q, d_q, step, bound)"""
+        return (int(self.q), int(self.ncand), float(self.alpha_q), float(self.d_q), float(self.step), float(self.bound))
+
+
+def copy_duals_batch(src, dsts):
+    """d and kind of `src` (BLU.set_duals) into every handle of `dsts` that holds src's matrix, device to device in one
+    launch; the kept row is not copied.  Returns the per-member statuses (ERROR_INVALID_CALL: another matrix or none).  A
+    refused call raises BluError, as does ERROR_DEVICE or ERROR_OUT_OF_MEMORY of a member."""
+    n = len(dsts)
+    L = lib()
+    L.blu_hip_copy_duals_batch.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p]
+    N = max(n, 1)
+    hs = (C.c_void_p * N)(*[h._h for h in dsts])
+    st = (C.c_int * N)()
+    rc = L.blu_hip_copy_duals_batch(src._h, hs, n, st)
+    out = [int(s) for s in st][:n]
+    if rc in (K.ERROR_ARGUMENT_MISSING, K.ERROR_INVALID_ARGUMENT) or (rc == K.ERROR_INVALID_CALL and out == [rc] * n):
+        raise BluError(rc, "copy_duals_batch refused")
+    for h, s in zip(dsts, out):
+        if s in (K.ERROR_DEVICE, K.ERROR_OUT_OF_MEMORY):
+            raise BluError(s, h.last_error() or src.last_error())
+    return out
+
+
+def ratio_test_batch(handles, rows, sigmas, pivtol, dualtol, prepare_update=False, want_solution=False):
+    """BLU.ratio_test(rows[k], sigmas[k], pivtol, dualtol, prepare_update) for len(handles) handles that hold one matrix in
+    one call: per member the status, the record, the kept row, the solution and the statistics of the single call.
+    Returns (statuses, records) with records[k] = (q, ncand, alpha_q, d_q, step, bound), None where the status is not OK.
+    A refused call raises BluError, as does ERROR_DEVICE or ERROR_OUT_OF_MEMORY of a member."""
+    n = len(handles)
+    if len(rows) != n or len(sigmas) != n:
+        raise ValueError("ratio_test_batch: one row and one sigma per handle")
+    L = lib()
+    L.blu_hip_ratio_test_batch.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_void_p, C.c_double, C.c_double] + [C.c_void_p] * 5
+    N = max(n, 1)
+    hs = (C.c_void_p * N)(*[h._h for h in handles])
+    rr = (C.c_int64 * N)(*[int(r) for r in rows])
+    sg = (C.c_double * N)(*[float(s) for s in sigmas])
+    recs = (RatioResult * N)()
+    pil, pl = (C.c_void_p * N)(), (C.c_void_p * N)()
+    if want_solution:
+        for k, h in enumerate(handles):
+            h._clear_lhs()
+            pil[k], pl[k] = h.ilhs.ctypes.data, h.lhs.ctypes.data or 8
+    nzl = (C.c_int64 * N)()
+    st = (C.c_int * N)()
+    rc = L.blu_hip_ratio_test_batch(hs, n, rr, int(bool(prepare_update)), sg, float(pivtol), float(dualtol), recs,
+                                    nzl if want_solution else None, pil if want_solution else None, pl if want_solution else None, st)
+    out = [int(s) for s in st][:n]
+    if rc == K.ERROR_INVALID_ARGUMENT and not all(np.isfinite(t) and t >= 0 for t in (float(pivtol), float(dualtol))):
+        raise BluError(rc, "ratio_test_batch refused: pivtol and dualtol are finite and not negative")
+    _matrix_batch_refused(rc, handles, "ratio_test_batch")
+    for k, (h, s) in enumerate(zip(handles, out)):
+        if s in (K.ERROR_DEVICE, K.ERROR_OUT_OF_MEMORY):
+            raise BluError(s, h.last_error() or handles[0].last_error())
+        if s == K.OK and want_solution:
+            h.nzlhs = int(nzl[k])
+    return out, [recs[k].as_tuple() if out[k] == K.OK else None for k in range(n)]
+
+
+def update_duals_batch(handles, thetas, sets=None):
+    """BLU.update_duals(thetas[k], *sets[k]) per member in one call; sets[k] is (jset, dset, kset) or None.  Returns the
+    per-member statuses.  A refused call raises BluError, as does ERROR_DEVICE or ERROR_OUT_OF_MEMORY of a member."""
+    n = len(handles)
+    if len(thetas) != n or (sets is not None and len(sets) != n):
+        raise ValueError("update_duals_batch: one theta (and one set or None) per handle")
+    L = lib()
+    L.blu_hip_update_duals_batch.argtypes = [C.c_void_p, C.c_int] + [C.c_void_p] * 6
+    N = max(n, 1)
+    hs = (C.c_void_p * N)(*[h._h for h in handles])
+    th = (C.c_double * N)(*[float(t) for t in thetas])
+    ns = (C.c_int64 * N)()
+    pj, pd, pk = (C.c_void_p * N)(), (C.c_void_p * N)(), (C.c_void_p * N)()
+    keep = []
+    for k in range(n):
+        if sets is None or sets[k] is None:
+            continue
+        j, d, kd = _dual_sets(*sets[k])
+        keep.append((j, d, kd))
+        ns[k] = len(j)
+        pj[k], pd[k], pk[k] = j.ctypes.data or 8, d.ctypes.data or 8, kd.ctypes.data or 8
+    st = (C.c_int * N)()
+    rc = L.blu_hip_update_duals_batch(hs, n, th, ns, pj, pd, pk, st)
+    _matrix_batch_refused(rc, handles, "update_duals_batch")
+    out = [int(s) for s in st][:n]
+    for h, s in zip(handles, out):
+        if s in (K.ERROR_DEVICE, K.ERROR_OUT_OF_MEMORY):
+            raise BluError(s, h.last_error() or handles[0].last_error())
+    del keep
+    return out
+
+
+def _dual_sets(jset, dset, kset):
+    j = np.ascontiguousarray(jset, dtype=np.int64)
+    d = np.ascontiguousarray(dset, dtype=np.float64)
+    kd = np.ascontiguousarray(kset, dtype=np.int8)
+    if not (len(j) == len(d) == len(kd)):
+        raise ValueError("update_duals: jset, dset and kset need one length")
+    return j, d, kd
+
+
 class BLU:
     """`struct BLU` (src/blu.rs:9-20) backed by the HIP implementation."""
 
@@ -859,6 +968,78 @@ class BLU:
         if st != K.OK:
             raise BluError(st, self.last_error())
         return z
+
+    # --- the ratio test on the device (blu_ratio.inc) -----------------------------------------------------
+    def set_duals(self, d=None, kind=None):
+        """Upload the reduced costs d and / or the bound status kind (0 no candidate, 1 at lower, -1 at upper, 2 free) of the
+        ncol columns of the resident matrix; None keeps the previous content, the first call needs both.  Returns the
+        status; ERROR_DEVICE and ERROR_OUT_OF_MEMORY raise."""
+        ncol = getattr(self, "_ncol", 0)
+        dd = None if d is None else np.ascontiguousarray(d, dtype=np.float64)
+        kk = None if kind is None else np.ascontiguousarray(kind, dtype=np.int8)
+        for a in (dd, kk):
+            if a is not None and a.shape != (ncol,):
+                raise ValueError("set_duals: d and kind need ncol entries")
+        L = lib()
+        L.blu_hip_set_duals.argtypes = [C.c_void_p] * 3
+        st = L.blu_hip_set_duals(self._h, None if dd is None else dd.ctypes.data or 8, None if kk is None else kk.ctypes.data or 8)
+        if st in (K.ERROR_DEVICE, K.ERROR_OUT_OF_MEMORY):
+            raise BluError(st, self.last_error())
+        return st
+
+    def get_duals(self):
+        """(status, d, kind) as the device holds them"""
+        ncol = getattr(self, "_ncol", 0)
+        d, kind = np.zeros(ncol), np.zeros(ncol, np.int8)
+        L = lib()
+        L.blu_hip_get_duals.argtypes = [C.c_void_p] * 3
+        st = L.blu_hip_get_duals(self._h, d.ctypes.data or 8, kind.ctypes.data or 8)
+        if st in (K.ERROR_DEVICE, K.ERROR_OUT_OF_MEMORY):
+            raise BluError(st, self.last_error())
+        return st, d, kind
+
+    def ratio_row(self):
+        """(status, alpha): the row the last successful ratio test on this handle kept, +0.0 where kind was 0"""
+        alpha = np.zeros(getattr(self, "_ncol", 0))
+        L = lib()
+        L.blu_hip_get_ratio_row.argtypes = [C.c_void_p] * 2
+        st = L.blu_hip_get_ratio_row(self._h, alpha.ctypes.data or 8)
+        if st in (K.ERROR_DEVICE, K.ERROR_OUT_OF_MEMORY):
+            raise BluError(st, self.last_error())
+        return st, alpha
+
+    def ratio_test(self, r, sigma, pivtol, dualtol, prepare_update=False, want_solution=False):
+        """The dual ratio test on row r of B^-1 A, on the device: the transposed solve of tableau_row(r, prepare_update),
+        the row into the kept-row buffer, and the selection rule of include/blu_hip.h over it and the resident d and
+        kind.  Returns (status, (q, ncand, alpha_q, d_q, step, bound)), the record None unless the status is OK; 64 bytes
+        are downloaded, plus the solution with want_solution."""
+        rec = RatioResult()
+        nz = C.c_int64(0)
+        L = lib()
+        L.blu_hip_ratio_test.argtypes = [C.c_void_p, C.c_int64, C.c_int, C.c_double, C.c_double, C.c_double] + [C.c_void_p] * 4
+        if want_solution:
+            self._clear_lhs()
+            st = L.blu_hip_ratio_test(self._h, int(r), int(bool(prepare_update)), float(sigma), float(pivtol), float(dualtol),
+                                      C.addressof(rec), C.addressof(nz), self.ilhs.ctypes.data, self.lhs.ctypes.data or 8)
+        else:
+            st = L.blu_hip_ratio_test(self._h, int(r), int(bool(prepare_update)), float(sigma), float(pivtol), float(dualtol),
+                                      C.addressof(rec), None, None, None)
+        if st == K.OK and want_solution:
+            self.nzlhs = int(nz.value)
+        elif st in (K.ERROR_DEVICE, K.ERROR_OUT_OF_MEMORY):
+            raise BluError(st, self.last_error())
+        return st, rec.as_tuple() if st == K.OK else None
+
+    def update_duals(self, theta, jset=(), dset=(), kset=()):
+        """The dual step d[j] -= theta * row[j] where kind[j] != 0, row being the kept row, then the overrides
+        d[jset[t]] = dset[t], kind[jset[t]] = kset[t].  Returns the status."""
+        j, d, kd = _dual_sets(jset, dset, kset)
+        L = lib()
+        L.blu_hip_update_duals.argtypes = [C.c_void_p, C.c_double, C.c_int64] + [C.c_void_p] * 3
+        st = L.blu_hip_update_duals(self._h, float(theta), len(j), j.ctypes.data or 8, d.ctypes.data or 8, kd.ctypes.data or 8)
+        if st in (K.ERROR_DEVICE, K.ERROR_OUT_OF_MEMORY):
+            raise BluError(st, self.last_error())
+        return st
 
     def dbg_matrix_counts(self):
         """The last price, or the last tableau_row behind its solve: (kernel launches, synchronizes, host-to-device

@@ -53,6 +53,7 @@ using pv_wave2::k_pivot_loop_wave2_r3;
 #include "k_update.hip"
 #include "k_copy.hip"
 #include "k_matrix.hip"
+#include "k_ratio.hip"
 
 #define BLU_STOPPED_STATUS 100 /* debug stepping only */
 
@@ -69,6 +70,8 @@ struct MatShare {
     char *bt;         // y tiles, products, masks and scatter descriptors of one chunk of a batched call
     size_t bt_cap;
     int64_t bt_limit; // debug: byte limit of bt (< 0: the default)
+    char *rt;         // blu_hip_ratio_test_batch: the pick descriptors and the records of one chunk
+    size_t rt_cap;
 };
 
 struct blu_hip {
@@ -164,6 +167,16 @@ struct blu_hip {
     int64_t mx_counts[4];        // last tableau_row (behind its solve) or price: launches, synchronizes, uploads, bytes downloaded
     int mx_timing;               // debug: 1 = events around k_at_dot
     double mx_kernel_s;          // ... its device seconds in the last call
+    // the resident duals (blu_ratio.inc): reduced costs, bound status and the kept row of the last ratio test, ncol each, in
+    // buffers of their own from the first blu_hip_set_duals on; the record of the pick and the overrides of a dual step
+    bool du_set, du_row_valid;
+    double *du_d, *du_row;
+    signed char *du_kind;
+    int64_t du_cap;              // entries the three hold
+    std::vector<signed char> du_hkind; // host mirror of du_kind (every change of kind comes from the host)
+    RatioRec *du_rec;
+    DualSet *du_sets;
+    int64_t du_setcap;
     // blu_hip_copy_batch (blu_copy.inc) with this handle as the source: the staging block on the device (segment table,
     // destination pointers, the destinations' descriptors), kept for the next call, and the counts of the last call
     char *cp_stage;
@@ -246,6 +259,7 @@ static void free_multi(blu_hip *h);
 static void free_sparse_multi(blu_hip *h);
 static void free_maxvolume(blu_hip *h);
 static void free_matrix(blu_hip *h);
+static void du_drop(blu_hip *h); // (blu_ratio.inc)
 static void free_all(blu_hip *h)
 {
     DevLU &D = h->D;
@@ -408,6 +422,13 @@ extern "C" blu_hip *blu_hip_new(int64_t m, int64_t b_nz, int device)
     memset(h->mx_counts, 0, sizeof h->mx_counts);
     h->mx_timing = 0;
     h->mx_kernel_s = 0.0;
+    h->du_set = h->du_row_valid = false;
+    h->du_d = h->du_row = nullptr;
+    h->du_kind = nullptr;
+    h->du_cap = 0;
+    h->du_rec = nullptr;
+    h->du_sets = nullptr;
+    h->du_setcap = 0;
     h->cp_stage = nullptr;
     h->cp_stage_cap = 0;
     memset(h->cp_counts, 0, sizeof h->cp_counts);
@@ -1072,6 +1093,7 @@ extern "C" int blu_hip_solve_dense(blu_hip *h, const double *rhs, double *lhs, c
 static int solve_sparse_core(blu_hip *h, int64_t nzrhs, const uint64_t *irhs, const double *xrhs, int64_t *p_nzlhs, int64_t *ilhs, double *lhs,
                              int tr);
 #include "blu_matrix.inc"
+#include "blu_ratio.inc"
 #include "blu_copy.inc"
 
 // solve_sparse -- src/solve_sparse.rs:36-68, lu/solve_sparse.rs:11-360 (fresh factorization: nforrest == 0)

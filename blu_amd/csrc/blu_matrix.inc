@@ -17,6 +17,7 @@ static void free_matrix(blu_hip *h)
     dfree(h->mx_y); dfree(h->mx_out); dfree(h->mx_skip);
     h->mx_ycap = h->mx_colcap = 0;
     h->mx_set = false;
+    du_drop(h);
 }
 
 // what a handle with a matrix of ncol columns has besides A: y (m doubles), the products and the skip bytes (ncol each)
@@ -52,6 +53,7 @@ extern "C" int blu_hip_set_matrix(blu_hip *h, int64_t ncol, const uint64_t *a_p,
         if (a_i[base + q] >= (uint64_t)h->m) return BLU_ERROR_INVALID_ARGUMENT;
     if (hipSetDevice(h->device) != hipSuccess) return BLU_ERROR_DEVICE;
     h->mx_set = false; // (from here on the buffers change)
+    du_drop(h);
     const size_t N = (size_t)ncol;
     int st = mx_work_buffers(h, ncol);
     if (st != BLU_OK) return st;
@@ -79,6 +81,8 @@ static MatShare *mx_share_block(blu_hip *h)
     S->bt = nullptr;
     S->bt_cap = 0;
     S->bt_limit = -1;
+    S->rt = nullptr;
+    S->rt_cap = 0;
     h->mx_hp = S->hp.data();
     h->mx_share = S;
     return S;
@@ -104,6 +108,7 @@ extern "C" int blu_hip_share_matrix(blu_hip *src, blu_hip **dst, int n, int *sta
     std::vector<int> result(n, kPending);
     for (int k = 0; k < n; k++) {
         blu_hip *h = dst[k];
+        du_drop(h); // (the resident duals of a destination go, blu_ratio.inc)
         if (h->mx_share == S && h->mx_set) { // (holds it already)
             result[k] = BLU_OK;
             continue;
@@ -202,16 +207,13 @@ static int mx_product(blu_hip *h, const int64_t *skip, double *out)
     return BLU_OK;
 }
 
-extern "C" int blu_hip_tableau_row(blu_hip *h, int64_t r, int prepare_update, const int64_t *skip, double *alpha, int64_t *p_nzlhs,
-                                   int64_t *ilhs, double *lhs)
+// step one of blu_hip_tableau_row and blu_hip_ratio_test (blu_ratio.inc): the transposed solve of e_r, as the single entry
+// makes it; the solution is downloaded only if asked for
+static int mx_row_solve(blu_hip *h, int64_t r, int prepare_update, int64_t *p_nzlhs, int64_t *ilhs, double *lhs)
 {
-    if (!h) return BLU_ERROR_ARGUMENT_MISSING;
-    if (!h->mx_set) return BLU_ERROR_INVALID_CALL;
-    if (h->mx_ncol > 0 && !alpha) return BLU_ERROR_ARGUMENT_MISSING;
     const bool fetch = p_nzlhs && ilhs && lhs;
     const uint64_t ir = (uint64_t)r;
     int st;
-    // step one: the transposed solve of e_r, as the single entry makes it; the solution is downloaded only if asked for
     if (prepare_update) { // blu_hip_solve_for_update(h, ., [r], ., 'T') with a solution
         if (h->nupdate < 0) return BLU_ERROR_INVALID_CALL;
         if (h->m == 0) return BLU_ERROR_INVALID_ARGUMENT;
@@ -230,20 +232,35 @@ extern "C" int blu_hip_tableau_row(blu_hip *h, int64_t r, int prepare_update, co
         const double one = 1.0;
         st = solve_sparse_core(h, 1, &ir, &one, fetch ? p_nzlhs : nullptr, ilhs, lhs, 1);
     }
+    return st;
+}
+
+// the launch of k_scatter_lhs over the solution the solve left on the device, into the cleared mx_y; counts itself
+static void mx_scatter(blu_hip *h)
+{
+    const size_t M = (size_t)h->m;
+    hipLaunchKernelGGL(k_scatter_lhs, dim3((unsigned)std::min<size_t>((M + 255) / 256, 64)), dim3(256), 0, h->stream, h->sw.out, h->sw.ilhs,
+                       h->sw.xval, (int)M, h->mx_y);
+    h->mx_counts[0]++;
+}
+
+extern "C" int blu_hip_tableau_row(blu_hip *h, int64_t r, int prepare_update, const int64_t *skip, double *alpha, int64_t *p_nzlhs,
+                                   int64_t *ilhs, double *lhs)
+{
+    if (!h) return BLU_ERROR_ARGUMENT_MISSING;
+    if (!h->mx_set) return BLU_ERROR_INVALID_CALL;
+    if (h->mx_ncol > 0 && !alpha) return BLU_ERROR_ARGUMENT_MISSING;
+    int st = mx_row_solve(h, r, prepare_update, p_nzlhs, ilhs, lhs);
     if (st != BLU_OK) return st;
     // step two: alpha = A' y with y scattered from the compressed solution on the device
     memset(h->mx_counts, 0, sizeof h->mx_counts);
     if (h->mx_ncol == 0) return BLU_OK;
-    const size_t M = (size_t)h->m;
-    hipStream_t stream = h->stream;
-    if (!hip_ok(h, hipMemsetAsync(h->mx_y, 0, M * 8, stream), "hipMemset")) return BLU_ERROR_DEVICE;
+    if (!hip_ok(h, hipMemsetAsync(h->mx_y, 0, (size_t)h->m * 8, h->stream), "hipMemset")) return BLU_ERROR_DEVICE;
     if (skip) {
         st = mx_upload_skip(h, skip);
         if (st != BLU_OK) return st;
     }
-    hipLaunchKernelGGL(k_scatter_lhs, dim3((unsigned)std::min<size_t>((M + 255) / 256, 64)), dim3(256), 0, stream, h->sw.out, h->sw.ilhs,
-                       h->sw.xval, (int)M, h->mx_y);
-    h->mx_counts[0]++;
+    mx_scatter(h);
     return mx_product(h, skip, alpha);
 }
 

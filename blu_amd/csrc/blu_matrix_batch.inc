@@ -34,11 +34,51 @@ static MxBatchLayout mx_batch_layout(size_t M, size_t N, size_t groups)
     return L;
 }
 
+// blu_hip_ratio_test_batch (blu_ratio.inc): the products of a chunk are not downloaded; k_ratio_pick_batch picks on them
+// and stores each member's row into its kept-row buffer, and the records come down.  Indexed by member like hs.
+struct MxRatio {
+    const double *sigma;
+    double pivtol, dualtol;
+    blu_ratio_result *out;
+};
+
+// the pick of one chunk behind its k_at_dot_batch, on h0's stream: the descriptors (grown with the chunk, kept with the
+// shared matrix) uploaded, then one workgroup per member; the records lie behind the descriptors.  false: failed
+static bool mx_batch_pick(blu_hip *h0, blu_hip **hs, MatShare *S, const std::vector<int> &members, const double *dOut, size_t N, const MxRatio &rt,
+                          std::vector<PickSrc> &ps) // (ps: host memory that lives until the synchronize)
+{
+    const size_t cn = members.size(), rec0 = align_up(cn * sizeof(PickSrc)), want = rec0 + cn * sizeof(blu_ratio_result);
+    if (want > S->rt_cap) {
+        dfree(S->rt);
+        S->rt_cap = 0;
+        if (!hip_ok(h0, hipMalloc((void **)&S->rt, want), "hipMalloc")) {
+            (void)hipGetLastError();
+            S->rt = nullptr;
+            return false;
+        }
+        S->rt_cap = want;
+    }
+    ps.resize(cn);
+    for (size_t s = 0; s < cn; s++) {
+        blu_hip *h = hs[members[s]];
+        ps[s] = PickSrc{h->du_d, h->du_kind, h->du_row, rt.sigma[members[s]]};
+    }
+    const bool ok = hip_ok(h0, hipMemcpyAsync(S->rt, ps.data(), cn * sizeof(PickSrc), hipMemcpyHostToDevice, h0->stream), "h2d pick descriptors");
+    h0->mx_counts[2]++;
+    if (!ok) return false;
+    hipLaunchKernelGGL(k_ratio_pick_batch, dim3((unsigned)cn), dim3(PICK_THREADS_BATCH), 0, h0->stream, (const PickSrc *)S->rt, dOut, (int)N,
+                       rt.pivtol, rt.dualtol, (RatioRec *)(S->rt + rec0));
+    h0->mx_counts[0]++;
+    return true;
+}
+
 // Step two for the members in `live` (all hold the matrix hm holds): member k's products into outs[k].  ys == NULL: y is
 // scattered from the member's compressed solution on the device; else ys[k] is its dense y on the host.  Members a failed
 // step takes with it get BLU_ERROR_DEVICE (BLU_ERROR_OUT_OF_MEMORY if the block of one group cannot be had).
+// With rt (ys, skip and outs NULL) the masks come from the members' host mirrors of kind, and behind k_at_dot_batch the
+// chunk goes on as described at MxRatio: one more upload (the pick descriptors), one more launch, 64 bytes per member down.
 static void mx_batch_products(blu_hip *h0, blu_hip **hs, const std::vector<int> &live, const double *const *ys, const int64_t *const *skip,
-                              double *const *outs, std::vector<int> &result)
+                              double *const *outs, std::vector<int> &result, const MxRatio *rt = nullptr)
 {
     if (live.empty()) return;
     blu_hip *hm = hs[live[0]];
@@ -75,6 +115,8 @@ static void mx_batch_products(blu_hip *h0, blu_hip **hs, const std::vector<int> 
     std::vector<double> tile, down;
     std::vector<unsigned char> mask;
     std::vector<ScatterSrc> src;
+    std::vector<blu_ratio_result> recs;
+    std::vector<PickSrc> ps;
     if (h0->mx_timing) h0->mx_kernel_s = 0.0;
 
     for (size_t c0 = 0; c0 < live.size(); c0 += gc * ATB_G) {
@@ -101,13 +143,19 @@ static void mx_batch_products(blu_hip *h0, blu_hip **hs, const std::vector<int> 
             h0->mx_counts[2]++;
         }
         for (size_t s = 0; skip && s < cn; s++) any_skip = any_skip || skip[members[s]];
+        any_skip = any_skip || rt;
         if (ok && any_skip) { // bit t of mask[g * ncol + j]: member t of group g skips column j
             mask.assign(groups * N, 0);
             for (size_t s = 0; s < cn; s++) {
-                const int64_t *sk = skip[members[s]];
-                if (!sk) continue;
+                const int64_t *sk = rt ? nullptr : skip[members[s]];
+                const signed char *kd = rt ? hs[members[s]]->du_hkind.data() : nullptr;
+                if (!sk && !kd) continue;
                 unsigned char *row = mask.data() + (s / ATB_G) * N;
                 const unsigned char bit = (unsigned char)(1u << (s % ATB_G));
+                if (kd) { // (branch-free: ncol bytes per member, on the host, in every call)
+                    for (size_t j = 0; j < N; j++) row[j] |= (unsigned char)(kd[j] == 0 ? bit : 0);
+                    continue;
+                }
                 for (size_t j = 0; j < N; j++)
                     if (sk[j] != 0) row[j] |= bit;
             }
@@ -124,20 +172,33 @@ static void mx_batch_products(blu_hip *h0, blu_hip **hs, const std::vector<int> 
                                (int)N, (int)M, (int)cn, (int)nbx, dOut);
             h0->mx_counts[0]++;
             if (h0->mx_timing) (void)hipEventRecord(h0->ev[1], stream);
-            ok = hip_ok(h0, hipStreamSynchronize(stream), "k_at_dot_batch");
+            if (rt) ok = mx_batch_pick(h0, hs, S, members, dOut, N, *rt, ps);
+            ok = ok && hip_ok(h0, hipStreamSynchronize(stream), rt ? "k_ratio_pick_batch" : "k_at_dot_batch");
             h0->mx_counts[1]++;
             if (h0->mx_timing && ok) {
                 float ms = 0.0f;
                 if (hipEventElapsedTime(&ms, h0->ev[0], h0->ev[1]) == hipSuccess) h0->mx_kernel_s += 1e-3 * (double)ms;
             }
         }
-        if (ok) {
+        if (ok && rt) {
+            recs.resize(cn);
+            ok = hip_ok(h0, hipMemcpy(recs.data(), S->rt + align_up(cn * sizeof(PickSrc)), cn * sizeof(blu_ratio_result), hipMemcpyDeviceToHost),
+                        "d2h records");
+        } else if (ok) {
             down.resize(cn * N);
             ok = hip_ok(h0, hipMemcpy(down.data(), dOut, cn * N * sizeof(double), hipMemcpyDeviceToHost), "d2h products");
         }
         if (!ok) { // this chunk and what is behind it
             fail_members(h0, hs, std::vector<int>(live.begin() + (long)c0, live.end()), result, BLU_ERROR_DEVICE);
             return;
+        }
+        if (rt) {
+            h0->mx_counts[3] += (int64_t)(cn * sizeof(blu_ratio_result));
+            for (size_t s = 0; s < cn; s++) {
+                rt->out[members[s]] = recs[s];
+                hs[members[s]]->du_row_valid = true;
+            }
+            continue;
         }
         h0->mx_counts[3] += (int64_t)(cn * N * sizeof(double));
         for (size_t s = 0; s < cn; s++) memcpy(outs[members[s]], down.data() + s * N, N * sizeof(double));
@@ -158,22 +219,11 @@ static int mx_batch_refusal(blu_hip *const *hs, int n)
     return BLU_OK;
 }
 
-extern "C" int blu_hip_tableau_row_batch(blu_hip **hs, int n, const int64_t *r, int prepare_update, const int64_t *const *skip,
-                                         double *const *alpha, int64_t *nzlhs, int64_t *const *ilhs, double *const *lhs, int *status)
+// step one of blu_hip_tableau_row_batch and blu_hip_ratio_test_batch (blu_ratio.inc) for the members still pending in
+// result: the batched transposed solves of e_r[k]; afterwards no member is pending
+static void mx_batch_row_solves(blu_hip *h0, blu_hip **hs, int n, const int64_t *r, int prepare_update, int64_t *nzlhs, int64_t *const *ilhs,
+                                double *const *lhs, std::vector<int> &result)
 {
-    // refusals of the call as a whole: every status[k] carries the code, no handle is touched
-    if (!hs || !r || !alpha || n < 0) return refuse_all(status, n, BLU_ERROR_ARGUMENT_MISSING);
-    if (n == 0) return BLU_OK;
-    for (int k = 0; k < n; k++)
-        if (!hs[k] || (hs[k]->mx_set && hs[k]->mx_ncol > 0 && !alpha[k])) return refuse_all(status, n, BLU_ERROR_ARGUMENT_MISSING);
-    if (const int st = mx_batch_refusal(hs, n); st != BLU_OK) return refuse_all(status, n, st);
-    blu_hip *h0 = hs[0];
-    if (hipSetDevice(h0->device) != hipSuccess) return refuse_all(status, n, BLU_ERROR_DEVICE);
-
-    // per member, in the order of blu_hip_tableau_row: the matrix, then the refusals of its solve
-    std::vector<int> result(n, kPending);
-    for (int k = 0; k < n; k++)
-        if (!hs[k]->mx_set) result[k] = BLU_ERROR_INVALID_CALL;
     const bool fetch = nzlhs && ilhs && lhs;
     std::vector<char> gather((size_t)n, 0);
     std::vector<uint64_t> ir((size_t)n);
@@ -191,14 +241,33 @@ extern "C" int blu_hip_tableau_row_batch(blu_hip **hs, int n, const int64_t *r, 
         const std::vector<const double *> pxr((size_t)n, &one);
         solve_sparse_batch_core(h0, hs, n, nz.data(), pir.data(), pxr.data(), nzlhs, ilhs, lhs, 1, gather, result);
     }
+    for (int k = 0; k < n; k++)
+        if (result[k] == kPending) result[k] = BLU_ERROR_DEVICE;
+}
+
+extern "C" int blu_hip_tableau_row_batch(blu_hip **hs, int n, const int64_t *r, int prepare_update, const int64_t *const *skip,
+                                         double *const *alpha, int64_t *nzlhs, int64_t *const *ilhs, double *const *lhs, int *status)
+{
+    // refusals of the call as a whole: every status[k] carries the code, no handle is touched
+    if (!hs || !r || !alpha || n < 0) return refuse_all(status, n, BLU_ERROR_ARGUMENT_MISSING);
+    if (n == 0) return BLU_OK;
+    for (int k = 0; k < n; k++)
+        if (!hs[k] || (hs[k]->mx_set && hs[k]->mx_ncol > 0 && !alpha[k])) return refuse_all(status, n, BLU_ERROR_ARGUMENT_MISSING);
+    if (const int st = mx_batch_refusal(hs, n); st != BLU_OK) return refuse_all(status, n, st);
+    blu_hip *h0 = hs[0];
+    if (hipSetDevice(h0->device) != hipSuccess) return refuse_all(status, n, BLU_ERROR_DEVICE);
+
+    // per member, in the order of blu_hip_tableau_row: the matrix, then the refusals of its solve
+    std::vector<int> result(n, kPending);
+    for (int k = 0; k < n; k++)
+        if (!hs[k]->mx_set) result[k] = BLU_ERROR_INVALID_CALL;
+    mx_batch_row_solves(h0, hs, n, r, prepare_update, nzlhs, ilhs, lhs, result);
 
     // step two for the members whose solve ended well
     memset(h0->mx_counts, 0, sizeof h0->mx_counts);
     std::vector<int> live;
-    for (int k = 0; k < n; k++) {
-        if (result[k] == kPending) result[k] = BLU_ERROR_DEVICE;
+    for (int k = 0; k < n; k++)
         if (result[k] == BLU_OK) live.push_back(k);
-    }
     mx_batch_products(h0, hs, live, nullptr, skip, alpha, result);
     return batch_return(result, status);
 }

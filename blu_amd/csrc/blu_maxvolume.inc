@@ -19,7 +19,7 @@ static void mx_detach(blu_hip *h)
     MatShare *S = h->mx_share;
     if (!S) return;
     if (--S->refs == 0) {
-        dfree(S->ap); dfree(S->ai64); dfree(S->ai); dfree(S->ax); dfree(S->bt);
+        dfree(S->ap); dfree(S->ai64); dfree(S->ai); dfree(S->ax); dfree(S->bt); dfree(S->rt);
         delete S;
     }
     h->mx_share = nullptr;
@@ -118,6 +118,7 @@ extern "C" int blu_hip_maxvolume(blu_hip *h, int64_t ncol, const uint64_t *a_p, 
     }
     if (hipSetDevice(h->device) != hipSuccess) return done(BLU_ERROR_DEVICE);
     h->mx_set = false; // (blu_matrix.inc: the buffers of a set matrix get an A nobody validated)
+    du_drop(h);
     int st = mv_upload(h, ncol, a_p, a_i, a_x);
     if (st != BLU_OK) return done(st);
     st = mv_factorize(h, a_p, basis, nz);

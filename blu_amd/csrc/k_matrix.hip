@@ -36,14 +36,16 @@ __global__ __launch_bounds__(256) void k_scatter_lhs(const long long *__restrict
     }
 }
 
-__global__ __launch_bounds__(ATD_THREADS) void k_at_dot(MatA A, const double *__restrict__ y, const unsigned char *__restrict__ skip,
-                                                        int ncol, double *__restrict__ out)
+// by_kind (a constant at both call sites): the bytes are the kind[] of the resident duals (k_ratio.hip), and it is
+// kind[j] == 0 that skips column j
+static __device__ __forceinline__ void at_dot_body(MatA A, const double *__restrict__ y, const unsigned char *__restrict__ skip, const bool by_kind,
+                                                   int ncol, double *__restrict__ out)
 {
     const int lane = (int)(threadIdx.x & 63);
     const long long base = ((long long)blockIdx.x * (ATD_THREADS / 64) + (long long)(threadIdx.x >> 6)) * 64;
     if (base >= ncol) return; // (the whole wave)
     const long long j = base + lane;
-    const bool live = j < ncol && !(skip && skip[j]);
+    const bool live = j < ncol && !(skip && (by_kind ? skip[j] == 0 : skip[j] != 0));
     long long b = 0;
     int n = 0;
     if (live) {
@@ -67,6 +69,19 @@ __global__ __launch_bounds__(ATD_THREADS) void k_at_dot(MatA A, const double *__
         if (lane == l) s = p;
     }
     if (j < ncol) out[j] = s;
+}
+
+__global__ __launch_bounds__(ATD_THREADS) void k_at_dot(MatA A, const double *__restrict__ y, const unsigned char *__restrict__ skip,
+                                                        int ncol, double *__restrict__ out)
+{
+    at_dot_body(A, y, skip, false, ncol, out);
+}
+
+// blu_hip_ratio_test (blu_ratio.inc): the same products, a column skipped where kind[j] == 0
+__global__ __launch_bounds__(ATD_THREADS) void k_at_dot_kind(MatA A, const double *__restrict__ y, const signed char *__restrict__ kind,
+                                                             int ncol, double *__restrict__ out)
+{
+    at_dot_body(A, y, (const unsigned char *)kind, true, ncol, out);
 }
 
 // ---------------------------------------------------------------------------------------------------------------------

@@ -475,6 +475,88 @@ int blu_hip_price_batch(blu_hip **h, int n, const double *const *y, const int64_
  * reports its part behind the solves, summed over the chunks. */
 int blu_hip_dbg_set_matrix_batch_bytes(blu_hip *h, int64_t bytes);
 
+/* Ratio test on the device (no reference counterpart): the reduced costs d[ncol] and the bound status kind[ncol] of the
+ * columns of the resident matrix stay on the device, the dual ratio test picks the entering column there from the pivot
+ * row, and the dual step d -= theta * alpha_r is made from the row the handle kept.  With
+ * blu_hip_solve_for_update_column and blu_hip_update a dual simplex iteration downloads 64 bytes plus the FTRAN solution.
+ *
+ * kind[j]: 0 no candidate (basic, fixed), +1 at its lower bound, -1 at its upper bound, 2 free.  The state -- d, kind and
+ * the kept row, 17 ncol device bytes, with a host mirror of kind -- is the handle's own and no part of what
+ * blu_hip_copy_batch copies.  It is allocated at the first blu_hip_set_duals and dropped by blu_hip_set_matrix, by being a
+ * destination of blu_hip_share_matrix and by blu_hip_maxvolume; then the entries below answer BLU_ERROR_INVALID_CALL until
+ * the next blu_hip_set_duals.  blu_hip_tableau_row and blu_hip_price do not disturb the kept row.
+ *
+ * The selection rule, for sigma (exactly +1.0 or -1.0) and finite pivtol >= 0, dualtol >= 0 -- anything else is
+ * BLU_ERROR_INVALID_ARGUMENT before anything is touched.  alpha is the tableau row with alpha[j] = +0.0 where
+ * kind[j] == 0 (those columns are not read), a = |alpha|, s = sigma * alpha.  Column j is a candidate if kind == 1 and
+ * s > pivtol, or kind == -1 and s < -pivtol, or kind == 2 and a > pivtol; its bound_j = (|d_j| + dualtol) / a_j (the sum
+ * rounded once, then the quotient) and step_j = |d_j| / a_j; a NaN bound_j makes it no candidate, and a NaN alpha[j]
+ * fails every comparison.  ncand counts the candidates.  None: q = -1 and every floating result +0.0.  Otherwise
+ * theta = min bound_j, and q is, among the candidates with step_j <= theta, the one with the largest a_j, the smallest j
+ * among equal a_j.  A minimum and a maximum of a total order: no bit depends on launch geometry, n or chunking. */
+typedef struct blu_ratio_result {
+    int64_t q;      /* the entering column, -1: none */
+    int64_t ncand;
+    double alpha_q;
+    double d_q;
+    double step;    /* step_q */
+    double bound;   /* theta */
+    int64_t reserved[2];
+} blu_ratio_result;
+/* Uploads d[0..ncol) and / or kind[0..ncol); a NULL pointer keeps the previous content, the first call after a drop needs
+ * both (else BLU_ERROR_ARGUMENT_MISSING).  NULL h BLU_ERROR_ARGUMENT_MISSING; no matrix set BLU_ERROR_INVALID_CALL; a
+ * kind[j] outside {0, 1, -1, 2} BLU_ERROR_INVALID_ARGUMENT before anything is touched.  ncol == 0 is fine.  A kept row
+ * stays valid. */
+int blu_hip_set_duals(blu_hip *h, const double *d, const int8_t *kind);
+/* Downloads d and / or kind (NULL: not wanted).  BLU_ERROR_INVALID_CALL without duals. */
+int blu_hip_get_duals(blu_hip *h, double *d, int8_t *kind);
+/* Downloads the kept row: the alpha of the last blu_hip_ratio_test(_batch) that answered BLU_OK on this handle, +0.0 where
+ * kind was 0.  BLU_ERROR_INVALID_CALL without duals or without a valid kept row; NULL alpha while ncol > 0
+ * BLU_ERROR_ARGUMENT_MISSING. */
+int blu_hip_get_ratio_row(blu_hip *h, double *alpha);
+/* The pivot row r and the selection rule on it.  Step one is the solve of blu_hip_tableau_row(h, r, prepare_update, ...)
+ * through the same code: its refusals in its order, flop counters, marker, stored row eta, optional download of the
+ * solution.  Step two stays on the device: y cleared, k_scatter_lhs, k_at_dot with kind == 0 as the skip straight into the
+ * kept-row buffer, k_ratio_pick, one synchronize, one download of the 64-byte record into *out
+ * (blu_hip_dbg_matrix_counts: 3 launches, 1 synchronize, 0 uploads, 64 bytes).
+ * Refusals in front of the solve, in this order: NULL h BLU_ERROR_ARGUMENT_MISSING; no matrix, then no duals
+ * BLU_ERROR_INVALID_CALL; NULL out BLU_ERROR_ARGUMENT_MISSING; the argument checks of the selection rule.  A refusal,
+ * the solve's own included, leaves the kept row as it was.  Behind the solve the kept row is replaced: valid when the call
+ * answers BLU_OK (q == -1 included), invalid when step two fails (BLU_ERROR_DEVICE), the handle being as after the solve.
+ * ncol == 0 makes the solve alone and answers q = -1. */
+int blu_hip_ratio_test(blu_hip *h, int64_t r, int prepare_update, double sigma, double pivtol, double dualtol, blu_ratio_result *out,
+                       int64_t *p_nzlhs, int64_t *ilhs, double *lhs);
+/* The dual step d[j] = d[j] - theta * row[j] for every j with kind[j] != 0 (the product rounded once, then the difference;
+ * row is the kept row), then the nset overrides d[jset[t]] = dset[t], kind[jset[t]] = kset[t] -- the entering and the
+ * leaving column of a pivot.  NULL h, or NULL jset, dset or kset while nset > 0, BLU_ERROR_ARGUMENT_MISSING; no duals or no
+ * valid kept row (also with theta == 0.0) BLU_ERROR_INVALID_CALL; nset < 0, an index twice or outside [0, ncol), a kset
+ * outside {0, 1, -1, 2} BLU_ERROR_INVALID_ARGUMENT, nothing touched.  Cost: at most one upload (the overrides), at most
+ * two launches, one synchronize, nothing downloaded.  The kept row stays valid. */
+int blu_hip_update_duals(blu_hip *h, double theta, int64_t nset, const int64_t *jset, const double *dset, const int8_t *kset);
+/* d and kind of src into every dst[k], device to device: one upload of the destination table, one launch and one
+ * synchronize whatever n is.  The kept row is not copied; a destination keeps its own.  Refused as a whole as
+ * blu_hip_share_matrix refuses (src without duals: BLU_ERROR_INVALID_CALL).  Per member: a dst[k] that does not hold
+ * src's matrix BLU_ERROR_INVALID_CALL, BLU_ERROR_OUT_OF_MEMORY; the others are served regardless. */
+int blu_hip_copy_duals_batch(blu_hip *src, blu_hip **dst, int n, int *status);
+/* blu_hip_ratio_test(h[k], r[k], prepare_update, sigma[k], pivtol, dualtol, &out[k], ...) for n handles that hold one
+ * matrix, in one call: member k gets the status, the record, the kept row, the solution, the statistics and the later
+ * behaviour of the single entry.  Refused as a whole as blu_hip_tableau_row_batch refuses (NULL h, r, sigma or out
+ * BLU_ERROR_ARGUMENT_MISSING; a bad pivtol or dualtol BLU_ERROR_INVALID_ARGUMENT).  Per member, in this order: no matrix,
+ * then no duals BLU_ERROR_INVALID_CALL; a bad sigma[k] BLU_ERROR_INVALID_ARGUMENT; then the refusals of its solve; out[k]
+ * of such a member is not written.  Step one is the batched solve of blu_hip_tableau_row_batch.  Step two, per chunk: the
+ * tiles and k_at_dot_batch as there, the skip masks built from the host mirrors of kind, then k_ratio_pick_batch, one
+ * workgroup per member, which also stores the member's row into its kept-row buffer; one synchronize, one download of
+ * 64 bytes per member (blu_hip_dbg_matrix_counts(h[0]) per chunk: 3 launches, 1 synchronize, 3 uploads, 64 bytes per
+ * member -- independent of n and ncol). */
+int blu_hip_ratio_test_batch(blu_hip **h, int n, const int64_t *r, int prepare_update, const double *sigma, double pivtol, double dualtol,
+                             blu_ratio_result *out, int64_t *nzlhs, int64_t *const *ilhs, double *const *lhs, int *status);
+/* blu_hip_update_duals(h[k], theta[k], nset[k], jset[k], dset[k], kset[k]) per member; nset may be NULL (no overrides).
+ * Refused as a whole: NULL h, theta or h[k], n < 0 BLU_ERROR_ARGUMENT_MISSING; the same handle twice, two devices or
+ * members that do not hold one matrix BLU_ERROR_INVALID_ARGUMENT.  Per member the refusals of the single entry.  Cost: one
+ * packed upload (the steps and the overrides of all members), at most two launches, one synchronize. */
+int blu_hip_update_duals_batch(blu_hip **h, int n, const double *theta, const int64_t *nset, const int64_t *const *jset,
+                               const double *const *dset, const int8_t *const *kset, int *status);
+
 /* Copying a handle (no reference counterpart): the complete logical state of src goes into the n handles dst[0..n) of
  * the same m on the same device, so that many handles hold one factorization -- fresh or updated, a pending
  * blu_hip_solve_for_update included -- and the batch entries above can continue from it, each member its own way.

@@ -106,6 +106,23 @@ extern "C" {
     fn blu_hip_price_batch(
         h: *mut *mut BluHip, n: c_int, y: *const *const f64, skip: *const *const i64, z: *const *mut f64, status: *mut c_int,
     ) -> c_int;
+    fn blu_hip_set_duals(h: *mut BluHip, d: *const f64, kind: *const i8) -> c_int;
+    fn blu_hip_get_duals(h: *mut BluHip, d: *mut f64, kind: *mut i8) -> c_int;
+    fn blu_hip_get_ratio_row(h: *mut BluHip, alpha: *mut f64) -> c_int;
+    fn blu_hip_ratio_test(
+        h: *mut BluHip, r: i64, prepare_update: c_int, sigma: f64, pivtol: f64, dualtol: f64, out: *mut RatioResult, p_nzlhs: *mut i64,
+        ilhs: *mut i64, lhs: *mut f64,
+    ) -> c_int;
+    fn blu_hip_update_duals(h: *mut BluHip, theta: f64, nset: i64, jset: *const i64, dset: *const f64, kset: *const i8) -> c_int;
+    fn blu_hip_copy_duals_batch(src: *mut BluHip, dst: *mut *mut BluHip, n: c_int, status: *mut c_int) -> c_int;
+    fn blu_hip_ratio_test_batch(
+        h: *mut *mut BluHip, n: c_int, r: *const i64, prepare_update: c_int, sigma: *const f64, pivtol: f64, dualtol: f64,
+        out: *mut RatioResult, nzlhs: *mut i64, ilhs: *const *mut i64, lhs: *const *mut f64, status: *mut c_int,
+    ) -> c_int;
+    fn blu_hip_update_duals_batch(
+        h: *mut *mut BluHip, n: c_int, theta: *const f64, nset: *const i64, jset: *const *const i64, dset: *const *const f64,
+        kset: *const *const i8, status: *mut c_int,
+    ) -> c_int;
     fn blu_hip_clone(src: *mut BluHip) -> *mut BluHip;
     fn blu_hip_last_error(h: *const BluHip) -> *const c_char;
 }
@@ -848,6 +865,123 @@ pub fn price_batch(
     let code = unsafe { blu_hip_price_batch(hs.as_mut_ptr(), n as c_int, py.as_ptr(), sk.as_ptr(), pz.as_ptr(), st.as_mut_ptr()) };
     if code == -3 || code == -4 {
         return status_of(code).map(|_| Vec::new()); // (codes only a refusal returns)
+    }
+    Ok(st.iter().map(|&s| status_of(s)).collect())
+}
+
+/// `blu_ratio_result` (include/blu_hip.h): what the ratio test on the device downloads, 64 bytes.
+#[repr(C)]
+#[derive(Clone, Copy, Debug, Default, PartialEq)]
+pub struct RatioResult {
+    pub q: i64,
+    pub ncand: i64,
+    pub alpha_q: f64,
+    pub d_q: f64,
+    pub step: f64,
+    pub bound: f64,
+    pub reserved: [i64; 2],
+}
+
+impl BLU {
+    /// Upload the reduced costs and / or the bound status (0 no candidate, 1 at lower, -1 at upper, 2 free) of the columns
+    /// of the resident matrix; `None` keeps the previous content, the first call needs both.
+    pub fn set_duals(&mut self, d: Option<&[f64]>, kind: Option<&[i8]>) -> Result<(), Status> {
+        let ncol = self.ncol.unwrap_or(0);
+        if d.map_or(false, |x| x.len() < ncol) || kind.map_or(false, |x| x.len() < ncol) {
+            return Err(Status::ErrorInvalidArgument);
+        }
+        status_of(unsafe { blu_hip_set_duals(self.lu.h, d.map_or(std::ptr::null(), |x| x.as_ptr()), kind.map_or(std::ptr::null(), |x| x.as_ptr())) })
+    }
+
+    pub fn get_duals(&mut self, d: &mut [f64], kind: &mut [i8]) -> Result<(), Status> {
+        let ncol = self.ncol.unwrap_or(0);
+        if d.len() < ncol || kind.len() < ncol {
+            return Err(Status::ErrorInvalidArgument);
+        }
+        status_of(unsafe { blu_hip_get_duals(self.lu.h, d.as_mut_ptr(), kind.as_mut_ptr()) })
+    }
+
+    /// The row the last successful ratio test kept, +0.0 where kind was 0.
+    pub fn ratio_row(&mut self, alpha: &mut [f64]) -> Result<(), Status> {
+        if alpha.len() < self.ncol.unwrap_or(0) {
+            return Err(Status::ErrorInvalidArgument);
+        }
+        status_of(unsafe { blu_hip_get_ratio_row(self.lu.h, alpha.as_mut_ptr()) })
+    }
+
+    /// The dual ratio test on row `r` of B^-1 A, on the device; the solution of the transposed solve is not downloaded.
+    pub fn ratio_test(&mut self, r: usize, prepare_update: bool, sigma: f64, pivtol: f64, dualtol: f64) -> Result<RatioResult, Status> {
+        let mut out = RatioResult::default();
+        status_of(unsafe {
+            blu_hip_ratio_test(
+                self.lu.h, r as i64, prepare_update as c_int, sigma, pivtol, dualtol, &mut out, std::ptr::null_mut(), std::ptr::null_mut(),
+                std::ptr::null_mut(),
+            )
+        })
+        .map(|_| out)
+    }
+
+    /// d[j] -= theta * row[j] where kind[j] != 0 (row: the kept row), then d[jset[t]] = dset[t], kind[jset[t]] = kset[t].
+    pub fn update_duals(&mut self, theta: f64, jset: &[i64], dset: &[f64], kset: &[i8]) -> Result<(), Status> {
+        if dset.len() != jset.len() || kset.len() != jset.len() {
+            return Err(Status::ErrorInvalidArgument);
+        }
+        status_of(unsafe { blu_hip_update_duals(self.lu.h, theta, jset.len() as i64, jset.as_ptr(), dset.as_ptr(), kset.as_ptr()) })
+    }
+}
+
+/// d and kind of `src` into every object of `dsts` that holds its matrix, device to device in one launch.
+pub fn copy_duals_batch(src: &mut BLU, dsts: &mut [&mut BLU]) -> Result<Vec<Result<(), Status>>, Status> {
+    let mut hs: Vec<*mut BluHip> = dsts.iter().map(|b| b.lu.h).collect();
+    let mut st = vec![0 as c_int; hs.len()];
+    let code = unsafe { blu_hip_copy_duals_batch(src.lu.h, hs.as_mut_ptr(), hs.len() as c_int, st.as_mut_ptr()) };
+    if code == -3 || code == -4 {
+        return status_of(code).map(|_| Vec::new()); // (codes only a refusal returns)
+    }
+    Ok(st.iter().map(|&s| status_of(s)).collect())
+}
+
+/// `ratio_test(rows[k], prepare_update, sigmas[k], pivtol, dualtol)` for objects that hold one matrix in one call.
+pub fn ratio_test_batch(
+    blus: &mut [&mut BLU], rows: &[usize], prepare_update: bool, sigmas: &[f64], pivtol: f64, dualtol: f64,
+) -> Result<Vec<Result<RatioResult, Status>>, Status> {
+    let n = blus.len();
+    if rows.len() != n || sigmas.len() != n {
+        return Err(Status::ErrorInvalidArgument);
+    }
+    let mut hs: Vec<*mut BluHip> = blus.iter().map(|b| b.lu.h).collect();
+    let r: Vec<i64> = rows.iter().map(|&x| x as i64).collect();
+    let mut out = vec![RatioResult::default(); n];
+    let mut st = vec![0 as c_int; n];
+    let code = unsafe {
+        blu_hip_ratio_test_batch(
+            hs.as_mut_ptr(), n as c_int, r.as_ptr(), prepare_update as c_int, sigmas.as_ptr(), pivtol, dualtol, out.as_mut_ptr(),
+            std::ptr::null_mut(), std::ptr::null(), std::ptr::null(), st.as_mut_ptr(),
+        )
+    };
+    if code == -3 {
+        return status_of(code).map(|_| Vec::new());
+    }
+    Ok((0..n).map(|k| status_of(st[k]).map(|_| out[k])).collect())
+}
+
+/// `update_duals(thetas[k], sets[k])` per member in one call; `sets[k]` is (jset, dset, kset).
+pub fn update_duals_batch(blus: &mut [&mut BLU], thetas: &[f64], sets: &[(&[i64], &[f64], &[i8])]) -> Result<Vec<Result<(), Status>>, Status> {
+    let n = blus.len();
+    if thetas.len() != n || sets.len() != n || sets.iter().any(|s| s.1.len() != s.0.len() || s.2.len() != s.0.len()) {
+        return Err(Status::ErrorInvalidArgument);
+    }
+    let mut hs: Vec<*mut BluHip> = blus.iter().map(|b| b.lu.h).collect();
+    let ns: Vec<i64> = sets.iter().map(|s| s.0.len() as i64).collect();
+    let pj: Vec<*const i64> = sets.iter().map(|s| s.0.as_ptr()).collect();
+    let pd: Vec<*const f64> = sets.iter().map(|s| s.1.as_ptr()).collect();
+    let pk: Vec<*const i8> = sets.iter().map(|s| s.2.as_ptr()).collect();
+    let mut st = vec![0 as c_int; n];
+    let code = unsafe {
+        blu_hip_update_duals_batch(hs.as_mut_ptr(), n as c_int, thetas.as_ptr(), ns.as_ptr(), pj.as_ptr(), pd.as_ptr(), pk.as_ptr(), st.as_mut_ptr())
+    };
+    if code == -3 {
+        return status_of(code).map(|_| Vec::new());
     }
     Ok(st.iter().map(|&s| status_of(s)).collect())
 }

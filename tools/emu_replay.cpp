@@ -48,6 +48,16 @@
 //               members after blu_hip_dbg_set_matrix_batch_bytes(bytes), every alpha of exactly ncol entries
 //   OP_PRICE_BATCH bytes nmem {has_skip skip[ncol if has_skip] y[m]}[nmem] rc {status [z[ncol] if status == 0]}[nmem]
 //               blu_hip_price_batch likewise
+//   OP_SET_DUALS d[ncol] kind[ncol] status                   blu_hip_set_duals with arrays of exactly ncol entries (kind one word each)
+//   OP_RATIO_TEST r prepare_update sigma pivtol dualtol status [q ncand alpha_q d_q step bound row[ncol] if status == 0]
+//               blu_hip_ratio_test, then blu_hip_get_ratio_row
+//   OP_UPDATE_DUALS theta nset jset[nset] dset[nset] kset[nset] status [d[ncol] kind[ncol] if status == 0]
+//               blu_hip_update_duals, then blu_hip_get_duals
+//   OP_COPY_DUALS                                           blu_hip_copy_duals_batch from the current handle into the holders
+//   OP_RATIO_TEST_BATCH bytes nmem {r sigma}[nmem] pivtol dualtol rc {status [record row[ncol] if status == 0]}[nmem]
+//               blu_hip_ratio_test_batch over the first nmem members, then blu_hip_get_ratio_row of each
+//   OP_UPDATE_DUALS_BATCH nmem {theta nset jset dset kset}[nmem] rc {status [d[ncol] kind[ncol] if status == 0]}[nmem]
+//               blu_hip_update_duals_batch, then blu_hip_get_duals of each
 //   OP_END
 #include "../include/blu_hip.h"
 
@@ -69,14 +79,16 @@ extern "C" int blu_hip_dbg_set_matrix_batch_bytes(blu_hip *h, int64_t bytes);
 
 enum { OP_END = 0, OP_NEW, OP_EXTRA, OP_PARAM, OP_FACT, OP_DENSE, OP_SPARSE, OP_FORUPD, OP_UPDATE, OP_STAT, OP_MULTI_WS, OP_DENSE_MULTI,
        OP_SPARSE_MULTI_WS, OP_SPARSE_MULTI, OP_SPARSE_MULTI_GET, OP_MAXVOLUME, OP_MAXVOLUME_CHUNK, OP_CLONE, OP_COPY_INTO, OP_SET_MATRIX,
-       OP_FACT_COLUMNS, OP_FORUPD_COLUMN, OP_TABLEAU_ROW, OP_PRICE, OP_SHARE_MATRIX, OP_TABLEAU_ROW_BATCH, OP_PRICE_BATCH };
+       OP_FACT_COLUMNS, OP_FORUPD_COLUMN, OP_TABLEAU_ROW, OP_PRICE, OP_SHARE_MATRIX, OP_TABLEAU_ROW_BATCH, OP_PRICE_BATCH,
+       OP_SET_DUALS, OP_RATIO_TEST, OP_UPDATE_DUALS, OP_COPY_DUALS, OP_RATIO_TEST_BATCH, OP_UPDATE_DUALS_BATCH };
 static const int64_t TAPE_MAGIC = 0x3145504154554c42LL; // "BLUTAPE1"
 static const char *const OP_NAME[] = {"end", "new", "dbg_set_upd_extra", "set_param", "factorize", "solve_dense", "solve_sparse",
                                       "solve_for_update", "update", "get_stat", "dbg_set_multi_ws_bytes", "solve_dense_multi",
                                       "dbg_set_sparse_multi_ws_bytes", "solve_sparse_multi", "get_sparse_multi", "maxvolume",
                                       "dbg_set_maxvolume_chunk", "clone", "copy_batch", "set_matrix", "factorize_columns",
                                       "solve_for_update_column", "tableau_row", "price", "share_matrix", "tableau_row_batch",
-                                      "price_batch"};
+                                      "price_batch", "set_duals", "ratio_test", "update_duals", "copy_duals_batch", "ratio_test_batch",
+                                      "update_duals_batch"};
 
 static std::vector<int64_t> tape;
 static size_t pos = 0;
@@ -127,6 +139,48 @@ static void same_words(const char *what, const void *got, const int64_t *want, s
     for (size_t k = 0; k < n; k++)
         if (memcmp(g + 8 * k, want + k, 8) != 0) differ(what, (long)k, g + 8 * k, want + k, is_double);
 }
+// the record of a ratio test, then the kept row of h
+static void same_pick(blu_hip *h, const blu_ratio_result &R, size_t ncol)
+{
+    same_int("q", R.q, word());
+    same_int("ncand", R.ncand, word());
+    const double x[4] = {R.alpha_q, R.d_q, R.step, R.bound};
+    same_words("record", x, take(4), 4, true);
+    same_int("reserved", R.reserved[0] | R.reserved[1], 0);
+    std::vector<double> row(ncol, -7.25e300);
+    same_int("get_ratio_row", blu_hip_get_ratio_row(h, row.data()), BLU_OK);
+    same_words("kept row", row.data(), take(ncol), ncol, true);
+}
+// d and kind of h
+static void same_duals(blu_hip *h, size_t ncol)
+{
+    std::vector<double> d(ncol, -7.25e300);
+    std::vector<int8_t> kind(ncol, 99);
+    same_int("get_duals", blu_hip_get_duals(h, d.data(), kind.data()), BLU_OK);
+    same_words("d", d.data(), take(ncol), ncol, true);
+    const int64_t *tk = take(ncol);
+    for (size_t j = 0; j < ncol; j++)
+        if (kind[j] != tk[j]) {
+            const int64_t g = kind[j];
+            differ("kind", (long)j, &g, tk + j, false);
+        }
+}
+struct DualSets { // the overrides of one dual step, arrays of exactly nset entries
+    std::vector<int64_t> j;
+    std::vector<double> d;
+    std::vector<int8_t> k;
+    void read()
+    {
+        const size_t n = (size_t)word();
+        const int64_t *tj = take(n);
+        j.assign(tj, tj + n);
+        const double *td = (const double *)take(n);
+        d.assign(td, td + n);
+        const int64_t *tk = take(n);
+        k.assign(tk, tk + n);
+    }
+};
+
 // status, and for a solve that succeeded nzlhs, the pattern in order and the bits of the dense solution
 static void same_solution(int status, int64_t m, int64_t nzlhs, const std::vector<int64_t> &ilhs, const std::vector<double> &lhs, bool want)
 {
@@ -163,7 +217,7 @@ int main(int argc, char **argv)
     std::vector<blu_hip *> holders; // of the last OP_SHARE_MATRIX
     for (;;) {
         op = word();
-        if (op < OP_END || op > OP_PRICE_BATCH) {
+        if (op < OP_END || op > OP_UPDATE_DUALS_BATCH) {
             fprintf(stderr, "emu_replay: unknown record %lld after call %ld\n", (long long)op, ncall);
             return 2;
         }
@@ -483,6 +537,85 @@ int main(int argc, char **argv)
                 same_int("nzlhs", nzlhs[k], word());
                 same_words("ilhs", ilhs[k].data(), take((size_t)nzlhs[k]), (size_t)nzlhs[k], false);
                 same_words("lhs", lhs[k].data(), take(M), M, true);
+            }
+            break;
+        }
+        case OP_SET_DUALS: {
+            const double *td = (const double *)take(ncol);
+            const std::vector<double> d(td, td + ncol);
+            const int64_t *tk = take(ncol);
+            const std::vector<int8_t> kind(tk, tk + ncol);
+            same_int("status", blu_hip_set_duals(h, d.data(), kind.data()), word());
+            break;
+        }
+        case OP_RATIO_TEST: {
+            const int64_t r = word();
+            const int prepare = (int)word();
+            const double sigma = real(), pivtol = real(), dualtol = real();
+            blu_ratio_result R;
+            const int status = blu_hip_ratio_test(h, r, prepare, sigma, pivtol, dualtol, &R, nullptr, nullptr, nullptr);
+            same_int("status", status, word());
+            if (status == BLU_OK) same_pick(h, R, ncol);
+            break;
+        }
+        case OP_UPDATE_DUALS: {
+            const double theta = real();
+            DualSets S;
+            S.read();
+            const int status = blu_hip_update_duals(h, theta, (int64_t)S.j.size(), S.j.data(), S.d.data(), S.k.data());
+            same_int("status", status, word());
+            if (status == BLU_OK) same_duals(h, ncol);
+            break;
+        }
+        case OP_COPY_DUALS: {
+            std::vector<int> status(holders.size(), -99);
+            same_int("return value", blu_hip_copy_duals_batch(h, holders.data(), (int)holders.size(), status.data()), BLU_OK);
+            for (int st : status) same_int("status", st, BLU_OK);
+            break;
+        }
+        case OP_RATIO_TEST_BATCH:
+        case OP_UPDATE_DUALS_BATCH: {
+            const bool pick = op == OP_RATIO_TEST_BATCH;
+            if (pick) same_int("status", blu_hip_dbg_set_matrix_batch_bytes(h, word()), BLU_OK);
+            const size_t nmem = (size_t)word();
+            if (nmem > holders.size() + 1) {
+                fprintf(stderr, "emu_replay: call %ld (%s) has more members than holders\n", ncall, OP_NAME[op]);
+                return 2;
+            }
+            std::vector<blu_hip *> hs(1, h);
+            hs.insert(hs.end(), holders.begin(), holders.begin() + (long)(nmem - 1));
+            std::vector<int64_t> r(nmem, 0), ns(nmem, 0);
+            std::vector<double> x(nmem, 0.0); // sigma or theta
+            std::vector<DualSets> sets(nmem);
+            std::vector<const int64_t *> pj(nmem);
+            std::vector<const double *> pd(nmem);
+            std::vector<const int8_t *> pk(nmem);
+            for (size_t k = 0; k < nmem; k++) {
+                if (pick) r[k] = word();
+                x[k] = real();
+                if (pick) continue;
+                sets[k].read();
+                ns[k] = (int64_t)sets[k].j.size();
+                pj[k] = sets[k].j.data();
+                pd[k] = sets[k].d.data();
+                pk[k] = sets[k].k.data();
+            }
+            std::vector<blu_ratio_result> recs(nmem);
+            std::vector<int> status(nmem, -99);
+            int rc;
+            if (pick) {
+                const double pivtol = real(), dualtol = real();
+                rc = blu_hip_ratio_test_batch(hs.data(), (int)nmem, r.data(), 0, x.data(), pivtol, dualtol, recs.data(), nullptr, nullptr, nullptr,
+                                              status.data());
+            } else {
+                rc = blu_hip_update_duals_batch(hs.data(), (int)nmem, x.data(), ns.data(), pj.data(), pd.data(), pk.data(), status.data());
+            }
+            same_int("return value", rc, word());
+            for (size_t k = 0; k < nmem; k++) {
+                same_int("status", status[k], word());
+                if (status[k] != BLU_OK) continue;
+                if (pick) same_pick(hs[k], recs[k], ncol);
+                else same_duals(hs[k], ncol);
             }
             break;
         }
